@@ -12,11 +12,15 @@ One "step" = one pass of the hot path over the whole grid, through the sharded-g
     match      this rank's share of the canonical grid (pair number p -> rank p % N)
     materialise  (query, train) lists compacted on the GPU and copied to pinned host memory
                ("incl. result materialisation on host"); the copy of step k overlaps step k+1
-The N = 1 line also carries configs[1] (100 x 2048 x 256, 4950 pairs) under "cfg2", the CPU baseline,
-the BA legs (cfg 4 / cfg 5; BA does not shard: "replicas only") and the two widened rows.
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs (with
+--dump-outputs) and the line.  Everything else is behind --full: the parity of the timed table against the
+CPU oracle's fixtures, the gather of every rank's lists to rank 0, the CPU baseline, and at N = 1 the chunk
+A/B, configs[1] (100 x 2048 x 256, 4950 pairs) under "cfg2", the SIFT / ORB / mixed-magnitude grids, the BA
+legs (cfg 4 / cfg 5; BA does not shard: "replicas only"), the epipolar filter and cfg 1.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+--dump-outputs DIR writes what the last timed step handed its caller as .npy files (see dump_outputs).
 `python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself (a child
 `python -m torch.distributed.run`, before this process has touched the GPU); fewer than N visible devices is an
 error (exit 2) -- it never falls back to a smaller world.
@@ -475,9 +479,50 @@ class PinnedLists:
     def wait(self):
         self.ctx.check(self.ctx.lib.rcn_match_compact_wait(self.ctx.h))
 
+    def last(self):
+        """(offsets, (total, 2) int32 view of the (query, train) rows) of the last begin; call after wait()."""
+        b = (self.k - 1) & 1
+        offs = self.offs[b]
+        total = int(offs[-1])
+        assert 0 <= total <= self.capacity, (total, self.capacity)
+        if total == 0:
+            return offs, np.zeros((0, 2), np.int32)
+        return offs, np.ctypeslib.as_array((self.C.c_int32 * (2 * total)).from_address(self.ptr[b].value)).reshape(total, 2)
+
     def close(self):
         for p in self.ptr:
             self.ctx.lib.rcn_host_free(p)
+
+
+def dump_outputs(dump_dir, counts, lists, P, world, rank, budget=60 * 10 ** 6, sample_pairs=2048):
+    """--dump-outputs: what the last timed step handed its caller, from this rank's tables and host lists.
+      pair_counts   float32 (P,)    matches per pair of this rank (row r = pair number r * world + rank)
+      sample_pairs  float64 (S,)    pair numbers of a fixed seeded sample of this rank's pairs
+      sample_lists  float32 (M, 2)  their (query, train) rows of the host lists, pair after pair
+    At N > 1 every rank writes its own files (suffix _rank<r>); all ranks together stay within `budget` bytes."""
+    os.makedirs(dump_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    room = budget // world
+    cnt = counts[:P].cpu().numpy() if P else np.zeros(0, np.int32)
+    rows, used = np.arange(P), 4 * P
+    if used > room // 4:           # a very large custom grid: a seeded sample of the counts as well (4 + 8 bytes per row)
+        rows = np.sort(np.random.default_rng(1).choice(P, room // 48, replace=False))
+        np.save(os.path.join(dump_dir, "pair_counts_pairs%s.npy" % sfx), (rows * world + rank).astype(np.float64))
+        used = 12 * len(rows)
+    np.save(os.path.join(dump_dir, "pair_counts%s.npy" % sfx), cnt[rows].astype(np.float32))
+    room -= used
+    pick, qt = np.zeros(0, np.int64), np.zeros((0, 2), np.int32)
+    if lists is not None and P:
+        pick = np.sort(np.random.default_rng(0).choice(P, min(P, sample_pairs), replace=False))
+        room -= 8 * len(pick)
+        offs, rows_qt = lists.last()
+        n = np.diff(offs)[pick]
+        keep = int(np.searchsorted(np.cumsum(8 * n), room, side="right"))     # whole pairs, within the room left
+        pick = pick[:keep]
+        if keep:
+            qt = np.concatenate([rows_qt[offs[p]:offs[p + 1]] for p in pick])
+    np.save(os.path.join(dump_dir, "sample_pairs%s.npy" % sfx), (pick * world + rank).astype(np.float64))
+    np.save(os.path.join(dump_dir, "sample_lists%s.npy" % sfx), qt.astype(np.float32))
 
 
 def parity_cfg2(out, counts):
@@ -559,10 +604,12 @@ def gather_leg(torch, dist, dev, shard, out, counts, K, P, n_img, world, rank, f
     return res
 
 
-def run_grid(torch, dist, dev, shard, n_img, K, local_dev, steps, warmup, world, materialise=True, check=None, gather_rank=None):
+def run_grid(torch, dist, dev, shard, n_img, K, local_dev, steps, warmup, world, materialise=True, check=None, gather_rank=None,
+             dump=None):
     """warmup + `steps` timed steps of exchange -> match -> materialise through the sharded-grid ABI.
     Returns (seconds of the timed region on this rank, stats of the timed steps, matches found, lists bytes).
-    gather_rank: this process's rank when the gather leg is to run behind the timed region (st["gather"])."""
+    gather_rank: this process's rank when the gather leg is to run behind the timed region (st["gather"]).
+    dump: (directory, rank) when the last step's outputs are to be written there (dump_outputs)."""
     ctx = shard.ctx
     shard.reserve(n_img, K, D)
     info0 = shard.info()
@@ -617,6 +664,8 @@ def run_grid(torch, dist, dev, shard, n_img, K, local_dev, steps, warmup, world,
     shard.profile(False)
     n_matches = int(counts[:P].sum().item()) if P else 0
     list_bytes = 8 * (lists.total.value if lists is not None else 0)
+    if dump is not None:
+        dump_outputs(dump[0], counts, lists, P, world, dump[1])
     if lists is not None:
         lists.close()
     st["parity"] = check(out, counts) if check is not None else None      # outside the timed region: the table is still in HBM
@@ -848,9 +897,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ba", action="store_true", help="skip the BA / epipolar / sweep legs")
     ap.add_argument("--no-cfg2", action="store_true", help="skip the configs[1] sub-measurement of the N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle parity, the gather to rank 0, the CPU baseline and (N = 1) the other legs; the --no-* switches thin it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, seeded sample, < 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)          # does not return
 
@@ -896,14 +951,21 @@ def main():
     # ---- inputs: every rank generates only the images it "detected"
     lo, hi = pairgrid.owned_images(n_img, world, rank)
     pool = synth.world_pool("superpoint", 4 * K, seed=1234)
-    local = np.stack([synth.image_descriptors("superpoint", i, K, pool, seed=1234) for i in range(lo, hi)]) if hi > lo \
-        else np.zeros((0, K, D), np.float32)
+    local = np.empty((hi - lo, K, D), np.float32)
+
+    def gen(i):                    # one counter-based generator per image: the same rows whatever the thread
+        local[i - lo] = synth.image_descriptors("superpoint", i, K, pool, seed=1234)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(host_threads()) as ex:
+        list(ex.map(gen, range(lo, hi)))
     local_dev = torch.from_numpy(local).to(dev) if hi > lo else torch.zeros((1, K, D), dtype=torch.float32, device=dev)
     n_pairs_total = n_img * (n_img - 1) // 2
 
     is_cfg = (n_img, K) == WORKLOADS[args.workload]
     main_check = parity_cfg3(world, rank) if (is_cfg and args.workload == "cfg3") else (parity_cfg2 if (is_cfg and args.workload == "cfg2" and world == 1) else None)
-    dt, st, n_matches, list_bytes, info = run_grid(torch, dist, dev, shard, n_img, K, local_dev, args.steps, args.warmup, world, check=main_check, gather_rank=rank)
+    dt, st, n_matches, list_bytes, info = run_grid(torch, dist, dev, shard, n_img, K, local_dev, args.steps, args.warmup, world,
+                                                   check=main_check if args.full else None, gather_rank=rank if args.full else None,
+                                                   dump=(args.dump_outputs, rank) if args.dump_outputs else None)
     par = st.get("parity") or {"equal_to_cpu": None, "pairs_compared": 0}
 
     tm = st["shard_times"]
@@ -933,7 +995,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f16+f64",
             "dtype_note": "f16 MFMA (f32 accumulate) coarse pass, f64 exact re-rank; indices bit-exact vs the f64 oracle",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "%s: %d images x %d keypoints x %d-d, %d image pairs, the same grid at every N (pair number p -> rank p %% N)"
                                    % (name, n_img, K, D, n_pairs_total),
                        "pairs_per_rank": int(info["n_pairs"]), "pair_matches_per_s": n_pairs_total * args.steps / dt,
@@ -941,7 +1003,7 @@ def main():
                        "exchange_bytes_f16_payload": int(info["exchange_bytes_f16"]), "exchange_bytes_f32_side_stream": int(info["exchange_bytes_f32"]),
                        "rows_reranked": rows[0], "rows_exact_fallback": rows[1], "rows_total": rows[2],
                        "hbm_used_gb_rank0": st.get("hbm_used_bytes", 0) / 1e9, "pipeline_chunks": int(st.get("chunks", 1)),
-                       # the table of the LAST timed step against the CPU oracle (outside the timed region): cfg3 = 5632 sampled
+                       # --full: the table of the LAST timed step against the CPU oracle (outside the timed region): cfg3 = 5632 sampled
                        # pairs by row hash + count (every residue of the pair number mod 8 x every sixteenth of the pair list), over all ranks; cfg2 = all 4950 pairs
                        "equal_to_cpu": par["equal_to_cpu"], "pairs_compared_with_cpu": par["pairs_compared"]},
             "roofline": roof,
@@ -959,7 +1021,7 @@ def main():
             line["rccl"]["value_with_gather"] = float(n_pairs_total) * K * K / (1e-3 * (ms_step + g["gather_ms"]))
             line["rccl"]["gather_note"] = ("all ranks' (query, train) lists in canonical pair order in rank 0's pinned host memory: compaction on every GPU, ncclSend / ncclRecv "
                                            "device to device, interleave on the root's GPU, one D2H copy; `value` is quoted without it (each rank's lists in its own host memory)")
-        if world == 1:
+        if world == 1 and args.full:
             if is_cfg and args.workload == "cfg3":
                 line["roofline"]["chunk_ab"] = chunk_ab_leg(torch, ctx, dev, n_img, K)
             if not args.no_cfg2 and args.workload != "cfg2":
@@ -995,9 +1057,9 @@ def main():
                 line["ba_lm_iterations_per_s"] = line["ba"]["cfg5"]["lm_iterations_per_s"]   # 1k cams / 100k pts / 1M obs
                 line["epipolar_filter"] = fmat_leg(ctx, not args.no_cpu_baseline)
                 line["cfg1"] = cfg1_leg(ctx, not args.no_cpu_baseline)
-        # the CPU baseline rides in EVERY line: rank 0 times the oracle on the same bounded sample of its own images behind
+        # the CPU baseline rides in every --full line: rank 0 times the oracle on the same bounded sample of its own images behind
         # the timed region while the other ranks wait at the closing barrier (at N > 1 they are idle: the host cores are rank 0's)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             images = [local[i] for i in range(min(local.shape[0], 64))]
             line["cpu_baseline"] = cpu_baseline(images, host_threads())
         else:

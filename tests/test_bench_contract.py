@@ -104,3 +104,42 @@ def test_bench_refuses_a_world_it_cannot_build():
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"rccl"' in src and "torch.distributed.run" in src
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_the_last_lists(tmp_path):
+    """--dump-outputs: every pair's count and the (query, train) rows of a seeded sample of pairs, exactly as the host lists
+    hold them, in float32 / float64 only, within the byte budget; the same lists give the same files."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(3)
+    P = 5000
+    cnt = rng.integers(0, 60, P).astype(np.int32)
+    offs = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    qt = rng.integers(0, 4096, (int(offs[-1]), 2)).astype(np.int32)
+
+    class Lists:
+        def last(self):
+            return offs, qt
+
+    def dump(d, world=1, rank=0, **kw):
+        bench.dump_outputs(str(d), torch.from_numpy(cnt), Lists(), P, world, rank, **kw)
+        sfx = "_rank%d" % rank if world > 1 else ""
+        files = {f: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        return [files[n + sfx + ".npy"] for n in ("pair_counts", "sample_pairs", "sample_lists")], sum(os.path.getsize(os.path.join(d, f)) for f in files)
+
+    (c, sp, sl), size = dump(tmp_path / "a")
+    assert size <= 64 * 10 ** 6 and np.array_equal(c, cnt) and len(sp) == 2048 and np.all(np.diff(sp) > 0)
+    rows = sp.astype(np.int64)
+    assert np.array_equal(sl, np.concatenate([qt[offs[p]:offs[p + 1]] for p in rows]).astype(np.float32))
+    (c2, sp2, sl2), _ = dump(tmp_path / "b")
+    assert np.array_equal(sp, sp2) and np.array_equal(sl, sl2)
+    # a tight budget keeps whole pairs only; at N > 1 the files carry the rank and the global pair numbers
+    (_, sp3, sl3), size3 = dump(tmp_path / "c", budget=200000)
+    assert 0 < len(sp3) < 2048 and len(sl3) == cnt[sp3.astype(np.int64)].sum() and size3 <= 200000 + 4 * 128
+    (c4, sp4, _), _ = dump(tmp_path / "d", world=2, rank=1)
+    assert np.array_equal(c4, cnt) and np.all(sp4.astype(np.int64) % 2 == 1)

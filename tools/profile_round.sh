@@ -11,8 +11,8 @@ O=gpurun_out/prof_$R
 mkdir -p "$O"
 run() { echo "== $*"; "$@" || echo "   (rc=$?)"; }
 if [ "$LEGS" != ba ]; then
-# ---- kernel time: the whole default bench (cfg3 headline + cfg2 + BA legs), no CPU baseline
-run rocprofv3 --kernel-trace --stats -d $O/trace_bench -o t --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/trace_bench.log 2>&1
+# ---- kernel time: the whole --full bench (cfg3 headline + cfg2 + BA legs), no CPU baseline
+run rocprofv3 --kernel-trace --stats -d $O/trace_bench -o t --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/trace_bench.log 2>&1
 # ---- kernel time of the dominant kernel at the headline shape alone (cfg3: every launch in this trace is a 1000 x 4096 x 256 launch)
 run rocprofv3 --kernel-trace --stats -d $O/trace_k1_cfg3 -o t --output-format csv -- python3 tools/k1_run.py 1000 4096 256 2 > $O/trace_k1_cfg3.log 2>&1
 # ---- K1 counters at cfg2 shape (100 x 2048 x 256) and at the SIFT shape (100 x 1500 x 128)
