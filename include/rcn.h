@@ -45,9 +45,10 @@ void        rcn_destroy(rcn_ctx *ctx);
 const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
 /* ABI revision of this header.  Bumped whenever a struct the library writes through a caller's pointer grows or an entry point changes
  * its arguments: a caller built against an older header must not be linked against a newer library (rcn_match_last_stats copies the whole
- * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library).
+ * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
+ * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 3
+#define RCN_ABI_REVISION 4
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -404,6 +405,15 @@ int  rcn_ba_session_validity(rcn_ba_session *s, const double *poses34_host, doub
 /* removeOutlierLandmarks (:956-976) for the flags of the last sweep: landmarks compacted on the device.
  * new_index_out (may be NULL): n_points entries before the call, -1 = removed. */
 int  rcn_ba_session_remove_outliers(rcn_ba_session *s, int32_t *new_index_out, int32_t *n_removed_out);
+/* triangulateMultiView for a batch of tracks (rcn_triangulate below) straight into the session: camera indices are session
+ * indices, poses34_host as in rcn_ba_session_validity, intrinsics the session's own.  Accepted tracks are appended as landmarks
+ * (track order, like landmarks.push_back) with their observations in track order; their coordinates go from the kernel into
+ * the session's point array without leaving HBM -- only the n_tracks status bytes come back.  The same as rcn_triangulate +
+ * rcn_ba_session_add_points + rcn_ba_session_add_observations on the same input, bit for bit.  status_out (n_tracks bytes),
+ * first_index_out (index of the first appended landmark), n_added_out may be NULL. */
+int  rcn_ba_session_triangulate(rcn_ba_session *s, const double *poses34_host, int32_t n_tracks, const int32_t *trk_off,
+                                const int32_t *obs_cam, const int32_t *obs_xy, double max_projection_error, double min_triangulation_angle,
+                                uint8_t *status_out, int32_t *first_index_out, int32_t *n_added_out);
 
 /* ---- landmark validity sweep -------------------------------------------------------------
  * SequentialReconstructor::checkLandmarkValidity (SequentialReconstructor.cpp:869-954), the check
@@ -441,6 +451,38 @@ int rcn_landmark_validity(rcn_ctx *ctx, const rcn_landmark_problem *problem, dou
 int rcn_landmark_validity_device(rcn_ctx *ctx, const rcn_landmark_problem *problem_dev, double max_projection_error,
                                  double min_triangulation_angle, uint8_t *out_inlier_dev, uint8_t *out_keep_dev,
                                  int32_t *out_n_inliers_dev);
+
+/* ---- multi-view triangulation ----------------------------------------------------------------
+ * SequentialReconstructor::triangulateMultiView (SequentialReconstructor.cpp:396-489) for a batch of tracks, one launch:
+ *   - unproject every observation (Camera.h:79-93: x = (u - cX) / fX, y = (v - cY) / fY, both minus k1 r + k2 r^2);
+ *   - A (2n x 4): rows x P.row(2) - P.row(0), y P.row(2) - P.row(1) with P = [R | t] (no K); X = the right singular vector
+ *     of A's smallest singular value, hnormalized (fp64: Givens QR of A streamed row by row, one-sided Jacobi on R);
+ *   - status 0 accepted; 1 that singular value is 0 or the WORLD z of X is not > 0 (the reference's test, :425);
+ *     2 an observation's L1 reprojection error exceeds max_projection_error (:447-451, no depth test);
+ *     3 SOME pair of rays subtends less than min_triangulation_angle "degrees" (pi = 3.1415, :458-478).
+ * Defaults of the reference: 4.0 px and 1.0 (SequentialReconstructor.h:256-257).  Layout as rcn_landmark_problem:
+ *   poses34 n_cams x 12, intrinsics n_cams x 6, trk_off n_tracks + 1 (CSR over the tracks, observations in the order of
+ *   the reference's matchedImgIdFeatId), obs_cam n_obs, obs_xy n_obs x 2 integer pixel coordinates.
+ * rcn_triangulate: host arrays; every track needs >= 2 observations (the reference reads singularValues()(3)), trk_off
+ * non-decreasing inside n_obs, cameras in range, else RCN_ERR_ARG; n_tracks == 0 is fine.  out_xyz (n_tracks x 3) holds
+ * every track's X, accepted or not; out_status n_tracks bytes; out_n_accepted may be NULL. */
+typedef struct {
+    int32_t        n_cams, n_tracks, n_obs, reserved;
+    const double  *poses34;
+    const double  *intrinsics;
+    const int32_t *trk_off;
+    const int32_t *obs_cam;
+    const int32_t *obs_xy;
+} rcn_triangulation_problem;
+int rcn_triangulate(rcn_ctx *ctx, const rcn_triangulation_problem *problem, double max_projection_error,
+                    double min_triangulation_angle, double *out_xyz, uint8_t *out_status, int32_t *out_n_accepted);
+/* Same with every pointer in DEVICE memory; asynchronous on the ctx stream, no graph check (a track of fewer than 2
+ * observations gets status 1).  out_n_accepted_dev (required) receives the count of accepted tracks; out_compact_dev (may be
+ * NULL) receives the X of the accepted tracks in track order at rows compact_first, compact_first + 1, ... (room for
+ * compact_first + n_tracks rows): a caller can append to an array of landmarks without a host round trip. */
+int rcn_triangulate_device(rcn_ctx *ctx, const rcn_triangulation_problem *problem_dev, double max_projection_error,
+                           double min_triangulation_angle, double *out_xyz_dev, uint8_t *out_status_dev,
+                           double *out_compact_dev, int32_t compact_first, int32_t *out_n_accepted_dev);
 
 /* ---- epipolar filter of a pair's matches --------------------------------------------------
  * GeometricFilter::estimateFundamental (GeometricFilter.cpp:39-61) as the pair loop uses it

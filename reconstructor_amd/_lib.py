@@ -31,7 +31,8 @@ SYMBOLS = [
     "rcn_ba_session_create", "rcn_ba_session_destroy", "rcn_ba_session_add_camera", "rcn_ba_session_cameras",
     "rcn_ba_session_add_points", "rcn_ba_session_add_observations", "rcn_ba_session_counts", "rcn_ba_session_graph",
     "rcn_ba_session_solve", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
-    "rcn_ba_session_remove_outliers",
+    "rcn_ba_session_remove_outliers", "rcn_ba_session_triangulate",
+    "rcn_triangulate", "rcn_triangulate_device",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -80,6 +81,13 @@ class LandmarkProblem(C.Structure):
                 ("reserved", C.c_int32),
                 ("poses34", C.c_void_p), ("intrinsics", C.c_void_p), ("points", C.c_void_p),
                 ("pt_off", C.c_void_p), ("obs_cam", C.c_void_p), ("obs_xy", C.c_void_p)]
+
+
+class TriangulationProblem(C.Structure):
+    _fields_ = [("n_cams", C.c_int32), ("n_tracks", C.c_int32), ("n_obs", C.c_int32),
+                ("reserved", C.c_int32),
+                ("poses34", C.c_void_p), ("intrinsics", C.c_void_p),
+                ("trk_off", C.c_void_p), ("obs_cam", C.c_void_p), ("obs_xy", C.c_void_p)]
 
 
 class BaOptions(C.Structure):
@@ -267,6 +275,12 @@ def load():
     L.rcn_ba_session_validity.argtypes = [vp, vp, C.c_double, C.c_double, vp, C.POINTER(i32), C.POINTER(i32)]
     L.rcn_ba_session_remove_outliers.restype = C.c_int
     L.rcn_ba_session_remove_outliers.argtypes = [vp, vp, C.POINTER(i32)]
+    L.rcn_ba_session_triangulate.restype = C.c_int
+    L.rcn_ba_session_triangulate.argtypes = [vp, vp, i32, vp, vp, vp, C.c_double, C.c_double, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.rcn_triangulate.restype = C.c_int
+    L.rcn_triangulate.argtypes = [vp, C.POINTER(TriangulationProblem), C.c_double, C.c_double, vp, vp, vp]
+    L.rcn_triangulate_device.restype = C.c_int
+    L.rcn_triangulate_device.argtypes = [vp, C.POINTER(TriangulationProblem), C.c_double, C.c_double, vp, vp, vp, i32, vp]
     L.rcn_store_save.restype = C.c_int
     L.rcn_store_save.argtypes = [C.c_char_p, C.POINTER(StoreContents)]
     L.rcn_store_open.restype = C.c_int

@@ -210,6 +210,24 @@ class BaSession:
         self.ctx.check(self.ctx.lib.rcn_ba_session_validity(self.h, p.ctypes.data, float(max_err), float(min_angle), inl.ctypes.data, C.byref(n_in), C.byref(n_er)))
         return inl[:self.counts()[1]].astype(bool), n_er.value
 
+    def triangulate(self, trk_off, obs_cam, obs_xy, poses34=None, max_err=4.0, min_angle=1.0):
+        """triangulateMultiView for a CSR batch of tracks (camera indices = session indices) straight into the session:
+        accepted tracks become landmarks (in track order) with their observations.  Returns (status per track, index of
+        the first new landmark, landmarks added)."""
+        if poses34 is None:
+            poses34 = poses34_from_angle_axis(self.cameras()[0])
+        p = np.ascontiguousarray(poses34, np.float64)
+        off = np.ascontiguousarray(trk_off, np.int32)
+        cam = np.ascontiguousarray(obs_cam, np.int32)
+        xy = np.ascontiguousarray(obs_xy, np.int32).reshape(-1, 2)
+        n = len(off) - 1
+        st = np.zeros(max(n, 1), np.uint8)
+        first, added = C.c_int32(), C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_triangulate(self.h, p.ctypes.data, n, off.ctypes.data, cam.ctypes.data if len(cam) else None,
+                                                               xy.ctypes.data if len(cam) else None, float(max_err), float(min_angle),
+                                                               st.ctypes.data, C.byref(first), C.byref(added)))
+        return st[:n], first.value, added.value
+
     def remove_outliers(self):
         npts = self.counts()[1]
         new_idx = np.zeros(max(1, npts), np.int32)

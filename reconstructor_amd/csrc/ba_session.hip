@@ -17,6 +17,7 @@
 #include "rcn_internal.h"
 
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <cmath>
 
@@ -68,6 +69,7 @@ struct rcn_ba_session {
     int64_t n_obs = 0;
     KeepBuf pts;                                     // n_points x 3 doubles, HBM
     DevBuf uv, ocam, opt, xy, pt_off, poses34, intr_dev, inl, keep, cnt, idx, tmp_pts;
+    DevBuf t_in, t_xyz, t_ws;                        // rcn_ba_session_triangulate: tracks staged in HBM, every track's X, workspace
     std::vector<int32_t> h_cam, h_pt;                // flattened graph (host), rebuilt with the device arrays
     std::vector<double> h_uv;
     bool obs_dirty = true;                           // device observation arrays do not reflect `tracks`
@@ -142,7 +144,8 @@ void rcn_ba_session_destroy(rcn_ba_session *s)
         (void)hipStreamSynchronize(ctx->stream);
         if ((ctx->ba_pair_token >> 32) == s->id) ctx->ba_pair_token = 0;
         s->pts.release();
-        DevBuf *bufs[] = {&s->uv, &s->ocam, &s->opt, &s->xy, &s->pt_off, &s->poses34, &s->intr_dev, &s->inl, &s->keep, &s->cnt, &s->idx, &s->tmp_pts};
+        DevBuf *bufs[] = {&s->uv, &s->ocam, &s->opt, &s->xy, &s->pt_off, &s->poses34, &s->intr_dev, &s->inl, &s->keep, &s->cnt, &s->idx, &s->tmp_pts,
+                          &s->t_in, &s->t_xyz, &s->t_ws};
         for (DevBuf *b : bufs) b->release();
     }
     delete s;
@@ -357,6 +360,73 @@ int rcn_ba_session_remove_outliers(rcn_ba_session *s, int32_t *new_index_out, in
     s->n_obs = no;
     s->obs_dirty = true;
     ++s->version;
+    return RCN_OK;
+}
+
+// triangulateMultiView for a batch of tracks straight into the session (triangulate.hip): the accepted tracks' X are
+// compacted by the kernels into the session's point array behind the landmarks already there; the host learns only the
+// status bytes and appends the accepted tracks to its mirror of the graph (landmarks.push_back, triangulatedFeatures in
+// track order).
+int rcn_ba_session_triangulate(rcn_ba_session *s, const double *poses34_host, int32_t n_tracks, const int32_t *trk_off,
+                               const int32_t *obs_cam, const int32_t *obs_xy, double max_projection_error, double min_triangulation_angle,
+                               uint8_t *status_out, int32_t *first_index_out, int32_t *n_added_out)
+{
+    if (!s || !poses34_host || n_tracks < 0 || (n_tracks > 0 && (!trk_off || !obs_cam || !obs_xy))) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (first_index_out) *first_index_out = np;
+    if (n_added_out) *n_added_out = 0;
+    if (n_tracks == 0) return RCN_OK;
+    const int32_t n_obs = trk_off[n_tracks];
+    int rc = rcn_int_triangulate_check(ctx, nc, n_tracks, n_obs, trk_off, obs_cam);
+    if (rc) return rc;
+    if ((int64_t)np + n_tracks > INT32_MAX) { ctx->set_error("rcn_ba_session_triangulate: too many landmarks"); return RCN_ERR_ARG; }
+    SES_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t nt = n_tracks, no = n_obs;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_off = 4 * (nt + 1), b_cam = 4 * no, b_xy = 8 * no;
+    SES_HIP(s->poses34.reserve(std::max(nc, 1) * 12 * sizeof(double)));
+    SES_HIP(s->intr_dev.reserve(std::max(nc, 1) * 6 * sizeof(double)));
+    SES_HIP(s->t_in.reserve(al(b_off) + al(b_cam) + al(b_xy) + al(nt) + 256));
+    SES_HIP(s->t_xyz.reserve(24 * nt));
+    SES_HIP(s->t_ws.reserve(rcn_int_triangulate_ws_bytes(nc, n_tracks)));
+    SES_HIP(s->cnt.reserve(16));
+    SES_HIP(s->pts.grow(((size_t)np + nt) * 24, (size_t)np * 24, st));          // room for every track behind the landmarks
+    char *in = s->t_in.as<char>();
+    int32_t *d_off = reinterpret_cast<int32_t *>(in), *d_cam = reinterpret_cast<int32_t *>(in + al(b_off)),
+            *d_xy = reinterpret_cast<int32_t *>(in + al(b_off) + al(b_cam));
+    uint8_t *d_st = reinterpret_cast<uint8_t *>(in + al(b_off) + al(b_cam) + al(b_xy));
+    SES_HIP(hipMemcpyAsync(s->poses34.p, poses34_host, (size_t)nc * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(s->intr_dev.p, s->intr.data(), (size_t)nc * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(d_off, trk_off, b_off, hipMemcpyHostToDevice, st));
+    if (no) {
+        SES_HIP(hipMemcpyAsync(d_cam, obs_cam, b_cam, hipMemcpyHostToDevice, st));
+        SES_HIP(hipMemcpyAsync(d_xy, obs_xy, b_xy, hipMemcpyHostToDevice, st));
+    }
+    rcn_triangulation_problem dp{nc, n_tracks, n_obs, 0, s->poses34.as<double>(), s->intr_dev.as<double>(), d_off, d_cam, d_xy};
+    rc = rcn_int_triangulate_launch(ctx, &dp, max_projection_error, min_triangulation_angle, s->t_ws.p, s->t_xyz.as<double>(), d_st,
+                                    static_cast<double *>(s->pts.p), np, s->cnt.as<int32_t>());
+    if (rc) return rc;
+    std::vector<uint8_t> status(nt);
+    int32_t added = 0;
+    SES_HIP(hipMemcpyAsync(status.data(), d_st, nt, hipMemcpyDeviceToHost, st));
+    SES_HIP(hipMemcpyAsync(&added, s->cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SES_HIP(hipStreamSynchronize(st));
+    int32_t n_acc = 0;
+    for (size_t j = 0; j < nt; ++j) {
+        if (status[j] != 0) continue;
+        std::vector<TrackObs> t;
+        for (int32_t o = trk_off[j]; o < trk_off[j + 1]; ++o) t.push_back(TrackObs{obs_cam[o], obs_xy[2 * (size_t)o], obs_xy[2 * (size_t)o + 1]});
+        s->n_obs += (int64_t)t.size();
+        s->tracks.push_back(std::move(t));
+        ++n_acc;
+    }
+    if (n_acc != added) { ctx->set_error("rcn_ba_session_triangulate: accepted count differs from the status bytes"); return RCN_ERR_HIP; }
+    if (n_acc) { s->obs_dirty = true; s->have_inlier = false; ++s->version; }
+    if (status_out) std::copy(status.begin(), status.end(), status_out);
+    if (n_added_out) *n_added_out = n_acc;
     return RCN_OK;
 }
 

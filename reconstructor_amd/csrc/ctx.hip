@@ -12,9 +12,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.3 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.4 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.3 (gfx950)";
+    return "reconstructor_amd 0.4 (gfx950)";
 #endif
 }
 
@@ -200,6 +200,8 @@ void rcn_destroy(rcn_ctx *ctx)
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : ctx->ba_ws) b.release();
     ctx->lm_ws.release();
+    ctx->tri_ws.release();
+    ctx->tri_dws.release();
     ctx->fm_ws.release();
     ctx->fm_state.release();
     ctx->fm_csr.release(); ctx->fm_pairs.release();

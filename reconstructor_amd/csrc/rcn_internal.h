@@ -179,6 +179,7 @@ struct rcn_ctx {
     // ---- BA state (ba.hip)
     DevBuf ba_ws[40];
     DevBuf lm_ws;              // landmark validity sweep (validity.hip)
+    DevBuf tri_ws, tri_dws;    // triangulation (triangulate.hip): host-API staging + workspace, workspace of the device entry
     DevBuf fm_ws, fm_state;    // epipolar filter (fmat.hip): host-API staging, per-pair RANSAC state
     std::vector<PairXY> fm_pairs_host;   // staging of fm_pairs (uploaded asynchronously)
     DevBuf fm_csr, fm_pairs;   // fused table filter: CSR of the matched points, per-pair coordinate pointers
@@ -252,6 +253,12 @@ struct BaResident {
 };
 int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res);
 int rcn_match_release(rcn_ctx *ctx);
+// triangulate.hip, with ctx->mu held: the host-side structure check, the workspace size and the launches (all pointers in
+// HBM; compact / n_accepted may be NULL)
+int rcn_int_triangulate_check(rcn_ctx *ctx, int32_t n_cams, int32_t n_tracks, int32_t n_obs, const int32_t *trk_off, const int32_t *obs_cam);
+size_t rcn_int_triangulate_ws_bytes(int32_t n_cams, int32_t n_tracks);
+int rcn_int_triangulate_launch(rcn_ctx *ctx, const rcn_triangulation_problem *dp, double max_err, double min_angle, void *ws,
+                               double *xyz, uint8_t *status, double *compact, int32_t compact_first, int32_t *n_accepted);
 // store.hip: rcn_match_compact_begin / _wait with ctx->mu already held
 int rcn_int_compact_begin(rcn_ctx *ctx, const int32_t *table_dev, int64_t stride, const int32_t *counts_dev,
                           int32_t n_pairs, int64_t *offsets_host, int32_t *qt_host, int64_t capacity, int64_t *total_out);

@@ -6,14 +6,14 @@
 // behind the camera (with the reference's erase-and-skip loop), then require at least one pair of
 // surviving observations whose viewing rays subtend more than the minimum angle.
 //
-//   V1 k_cam_centres   -R't of every camera, once                                   [trivial]
+//   V1 k_cam_centres   -R't of every camera, once (camgeom.h, shared with triangulate.hip)   [trivial]
 //   V2 k_landmark_sweep one thread per landmark, tracks walked in place (the erase loop needs no
 //                      list: position p of the shrinking list is original index p + erased)  [HBM gathers]
 //
 // Every operation is a separately rounded IEEE double (contraction off), in the order of the
 // oracle (oracle/validity_oracle.c), so the decisions agree with it bit for bit up to the last
 // ulp of acos.
-#include "rcn_internal.h"
+#include "camgeom.h"
 
 namespace {
 
@@ -26,31 +26,12 @@ struct SweepArgs {
     int32_t *n_inliers;
 };
 
-__global__ void k_cam_centres(const double *__restrict__ poses, int n_cams, double *__restrict__ centres)
-{
-#pragma clang fp contract(off)
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cams) return;
-    const double *P = poses + 12 * (size_t)c;
-    for (int i = 0; i < 3; ++i)
-        centres[3 * (size_t)c + i] = ((-P[i]) * P[3] + (-P[4 + i]) * P[7]) + (-P[8 + i]) * P[11];   // SequentialReconstructor.cpp:820
-}
-
 __device__ __forceinline__ bool observation_bad(const SweepArgs &a, const double *X, int o)
 {
-#pragma clang fp contract(off)
     const int c = a.obs_cam[o];
-    const double *P = a.poses + 12 * (size_t)c, *K = a.intr + 6 * (size_t)c;
-    double l[3];
-    for (int i = 0; i < 3; ++i) l[i] = ((P[4 * i] * X[0] + P[4 * i + 1] * X[1]) + P[4 * i + 2] * X[2]) + P[4 * i + 3];   // :842-848
-    double x = l[0] / l[2], y = l[1] / l[2];                                                                          // Camera.h:59-76
-    const double radius = x * x + y * y;
-    const double distortion = K[4] * radius + (K[5] * radius) * radius;
-    x += distortion;
-    y += distortion;
-    const double u = K[0] * x + K[2], v = K[1] * y + K[3];
-    const double resid = fabs(u - (double)a.obs_xy[2 * (size_t)o]) + fabs(v - (double)a.obs_xy[2 * (size_t)o + 1]);   // :852-867
-    return resid > a.max_err || l[2] < 0;                                                                             // :886-887
+    double depth;
+    const double resid = reproj_l1(a.poses + 12 * (size_t)c, a.intr + 6 * (size_t)c, X, a.obs_xy[2 * (size_t)o], a.obs_xy[2 * (size_t)o + 1], &depth);   // :842-867
+    return resid > a.max_err || depth < 0;                                                                                                     // :886-887
 }
 
 __global__ __launch_bounds__(128) void k_landmark_sweep(SweepArgs a)
@@ -76,15 +57,9 @@ __global__ __launch_bounds__(128) void k_landmark_sweep(SweepArgs a)
         for (int p = 0; p < k && !angle_ok; ++p) {
             if (!a.keep[o0 + p]) continue;
             const double *c1 = a.centres + 3 * (size_t)a.obs_cam[o0 + p];
-            const double r1[3] = {X[0] - c1[0], X[1] - c1[1], X[2] - c1[2]};
-            const double n1 = sqrt((r1[0] * r1[0] + r1[1] * r1[1]) + r1[2] * r1[2]);
             for (int q = p + 1; q < k; ++q) {
                 if (!a.keep[o0 + q]) continue;
-                const double *c2 = a.centres + 3 * (size_t)a.obs_cam[o0 + q];
-                const double r2[3] = {X[0] - c2[0], X[1] - c2[1], X[2] - c2[2]};
-                const double n2 = sqrt((r2[0] * r2[0] + r2[1] * r2[1]) + r2[2] * r2[2]);
-                const double dot = (r1[0] * r2[0] + r1[1] * r2[1]) + r1[2] * r2[2];
-                const double ang = 180.0 * acos(dot / (n1 * n2)) / 3.1415;      // :831-833
+                const double ang = tri_angle(X, c1, a.centres + 3 * (size_t)a.obs_cam[o0 + q]);   // :831-833
                 if (ang > a.min_angle) { angle_ok = true; break; }
             }
         }
