@@ -46,9 +46,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
 /* ABI revision of this header.  Bumped whenever a struct the library writes through a caller's pointer grows or an entry point changes
  * its arguments: a caller built against an older header must not be linked against a newer library (rcn_match_last_stats copies the whole
  * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
- * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem).
+ * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
+ * correspondence search and the attach entry points).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 4
+#define RCN_ABI_REVISION 5
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -415,6 +416,14 @@ int  rcn_ba_session_triangulate(rcn_ba_session *s, const double *poses34_host, i
                                 const int32_t *obs_cam, const int32_t *obs_xy, double max_projection_error, double min_triangulation_angle,
                                 uint8_t *status_out, int32_t *first_index_out, int32_t *n_added_out);
 
+/* Step 1 of triangulateMatchedLandmarks against the session's landmarks (rcn_landmark_attach's rules; camera `cam` of the
+ * session, poses34_host as in rcn_ba_session_validity, its intrinsics the session's own).  The points stay in HBM; only
+ * the status bytes come back (status_out, n_added_out may be NULL).  Attached entries are appended to their landmarks'
+ * tracks in list order: bit for bit rcn_landmark_attach + rcn_ba_session_add_observations of the attached entries. */
+int  rcn_ba_session_attach(rcn_ba_session *s, const double *poses34_host, int32_t cam, int32_t n, const int32_t *landmark,
+                           const int32_t *feat, const int32_t *xy, double max_projection_error, uint8_t *status_out,
+                           int32_t *n_added_out);
+
 /* ---- landmark validity sweep -------------------------------------------------------------
  * SequentialReconstructor::checkLandmarkValidity (SequentialReconstructor.cpp:869-954), the check
  * the reference runs on the observation graph before and after every bundle adjustment:
@@ -483,6 +492,60 @@ int rcn_triangulate(rcn_ctx *ctx, const rcn_triangulation_problem *problem, doub
 int rcn_triangulate_device(rcn_ctx *ctx, const rcn_triangulation_problem *problem_dev, double max_projection_error,
                            double min_triangulation_angle, double *out_xyz_dev, uint8_t *out_status_dev,
                            double *out_compact_dev, int32_t compact_first, int32_t *out_n_accepted_dev);
+
+/* ---- next view: 2D-3D correspondences, density score, attach ------------------------------------
+ * The deterministic part of SequentialReconstructor::addNextView (SequentialReconstructor.cpp:761-813).
+ *
+ * rcn_match_lists_upload: the directed lists featureMatches[(a, b)] (each injective), once, resident in the ctx until
+ * the next upload or rcn_match_lists_clear.  Layout of rcn_match_compact_begin: pairs n_pairs x (a, b) image ids,
+ * offsets n_pairs + 1 (int64, offsets[0] = 0), qt offsets[n_pairs] x (feature of a, feature of b) in any order within a
+ * pair.  mirror != 0: a directed pair that was not uploaded but whose reverse was is that reverse's inverse (the
+ * canonical i < j lists stand for featureMatches[(j, i)]); a pair given in both directions is read as given; a pair given
+ * in neither has no matches.  RCN_ERR_ARG: a repeated directed pair, a pair (a, a), a list that is not injective, a
+ * feature < 0 or >= K, an image without coordinates (rcn_coords_upload: the cells need them).
+ *
+ * rcn_corr_2d3d: calc2d3dMatches (:643-695) for every candidate, plus rankNextImages' density score (:714-744).
+ *   graph       n_points landmarks as CSR: pt_off (n_points + 1, pt_off[0] = 0), obs_img / obs_feat per observation in
+ *               triangulatedFeatures order
+ *   candidates  n_cand distinct image ids (the reference's std::set: ascending), cand_shape n_cand x (rows, cols)
+ *               (imgIdx2imgShape)
+ *   out         entries of candidate k at cand_off[k] .. cand_off[k + 1] (n_cand + 1 int64) in the reference's order:
+ *               landmark by landmark, each track in order; an observation (i, f) gives (landmark, g) when
+ *               featureMatches[(i, c)] maps f -> g (the same landmark or g may repeat; observations of c itself give
+ *               nothing); out_landmark / out_feat hold `capacity` entries (RCN_ERR_ARG with *total_out set when too small);
+ *               out_cells[k] = distinct cells (int)(32 x / cols), (int)(32 y / rows) inside 0 .. 31 (the MatchDensity
+ *               score); out_outside[k] (may be NULL) = entries whose cell falls outside (they stay in the lists).
+ * RCN_ERR_ARG: no lists, an (image, feature) observed twice in the graph (the reference's flow never does that: a
+ * feature gets one landmarkId), a feature outside its image's coordinates, a repeated candidate, a shape <= 0, a graph
+ * image or candidate without coordinates.  The reference's features[c][g]->landmarkId == -1 test is not modelled (it
+ * always holds for an unregistered image); the C++ adapter checks it.  Work and memory are bounded by the workspace
+ * budget (rcn_corr_set_workspace_bytes, default 1 GiB of hit rows: 4 bytes per observation per candidate of a batch);
+ * results do not depend on it. */
+int rcn_match_lists_upload(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, const int64_t *offsets, const int32_t *qt, int32_t mirror);
+int rcn_match_lists_clear(rcn_ctx *ctx);
+int rcn_corr_set_workspace_bytes(rcn_ctx *ctx, int64_t bytes);
+int rcn_corr_2d3d(rcn_ctx *ctx, int32_t n_points, const int32_t *pt_off, const int32_t *obs_img, const int32_t *obs_feat,
+                  int32_t n_cand, const int32_t *cand, const int32_t *cand_shape, int64_t *cand_off,
+                  int32_t *out_landmark, int32_t *out_feat, int64_t capacity, int64_t *total_out,
+                  int32_t *out_cells, int32_t *out_outside);
+/* Same with every pointer in DEVICE memory (n_obs = pt_off[n_points] given by the caller); asynchronous on the ctx stream
+ * after one small host-to-device copy (the coordinates' slot table); no graph check.  Malformed input cannot make the
+ * kernels read or write out of bounds: images without lists, features outside the coordinates and offsets outside
+ * 0 .. n_obs are ignored, entries past `capacity` are dropped (*total_dev still counts them).  An (image, feature)
+ * observed twice: only its first observation matches. */
+int rcn_corr_2d3d_device(rcn_ctx *ctx, int32_t n_points, int32_t n_obs, const int32_t *pt_off_dev, const int32_t *obs_img_dev,
+                         const int32_t *obs_feat_dev, int32_t n_cand, const int32_t *cand_dev, const int32_t *cand_shape_dev,
+                         int64_t *cand_off_dev, int32_t *out_landmark_dev, int32_t *out_feat_dev, int64_t capacity,
+                         int64_t *total_dev, int32_t *out_cells_dev, int32_t *out_outside_dev);
+/* Step 1 of triangulateMatchedLandmarks (:497-512) for the new view: entries (landmark, feature, integer pixel xy) in list
+ * order (the PnP inliers), the view's pose34 (12) and intrinsics (6), the landmarks' points (n_points x 3).  Entry e is
+ * attached iff its camera-frame depth > 0, its L1 reprojection error < max_projection_error (strict; NaN rejected) and no
+ * EARLIER ATTACHED entry has the same feature (a rejected entry blocks nothing).  status_out: 0 attached, 1 depth,
+ * 2 reprojection, 3 feature already taken -- the first failing rule.  fp64, the validity sweep's projection bit for bit.
+ * RCN_ERR_ARG: a landmark index outside 0 .. n_points - 1 or a negative feature.  n_attached_out may be NULL. */
+int rcn_landmark_attach(rcn_ctx *ctx, const double *pose34, const double *intr6, int32_t n_points, const double *points, int32_t n,
+                        const int32_t *landmark, const int32_t *feat, const int32_t *xy, double max_projection_error,
+                        uint8_t *status_out, int32_t *n_attached_out);
 
 /* ---- epipolar filter of a pair's matches --------------------------------------------------
  * GeometricFilter::estimateFundamental (GeometricFilter.cpp:39-61) as the pair loop uses it

@@ -33,6 +33,8 @@ SYMBOLS = [
     "rcn_ba_session_solve", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
     "rcn_ba_session_remove_outliers", "rcn_ba_session_triangulate",
     "rcn_triangulate", "rcn_triangulate_device",
+    "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
+    "rcn_landmark_attach", "rcn_ba_session_attach",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -281,6 +283,20 @@ def load():
     L.rcn_triangulate.argtypes = [vp, C.POINTER(TriangulationProblem), C.c_double, C.c_double, vp, vp, vp]
     L.rcn_triangulate_device.restype = C.c_int
     L.rcn_triangulate_device.argtypes = [vp, C.POINTER(TriangulationProblem), C.c_double, C.c_double, vp, vp, vp, i32, vp]
+    L.rcn_match_lists_upload.restype = C.c_int
+    L.rcn_match_lists_upload.argtypes = [vp, i32, vp, vp, vp, i32]
+    L.rcn_match_lists_clear.restype = C.c_int
+    L.rcn_match_lists_clear.argtypes = [vp]
+    L.rcn_corr_set_workspace_bytes.restype = C.c_int
+    L.rcn_corr_set_workspace_bytes.argtypes = [vp, i64]
+    L.rcn_corr_2d3d.restype = C.c_int
+    L.rcn_corr_2d3d.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
+    L.rcn_corr_2d3d_device.restype = C.c_int
+    L.rcn_corr_2d3d_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.rcn_landmark_attach.restype = C.c_int
+    L.rcn_landmark_attach.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
+    L.rcn_ba_session_attach.restype = C.c_int
+    L.rcn_ba_session_attach.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
     L.rcn_store_save.restype = C.c_int
     L.rcn_store_save.argtypes = [C.c_char_p, C.POINTER(StoreContents)]
     L.rcn_store_open.restype = C.c_int

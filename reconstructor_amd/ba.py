@@ -228,6 +228,23 @@ class BaSession:
                                                                st.ctypes.data, C.byref(first), C.byref(added)))
         return st[:n], first.value, added.value
 
+    def attach(self, cam, landmark, feat, xy, poses34=None, max_err=4.0):
+        """Step 1 of triangulateMatchedLandmarks against the session's landmarks (rcn_ba_session_attach): entries (landmark,
+        feature, xy) of camera `cam` in list order; attached ones are appended to their tracks.  Returns (status per entry:
+        0 attached, 1 depth, 2 reprojection, 3 feature taken; number attached)."""
+        if poses34 is None:
+            poses34 = poses34_from_angle_axis(self.cameras()[0])
+        p = np.ascontiguousarray(poses34, np.float64)
+        lm, ft = np.ascontiguousarray(landmark, np.int32), np.ascontiguousarray(feat, np.int32)
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = len(lm)
+        st = np.zeros(max(n, 1), np.uint8)
+        added = C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_attach(self.h, p.ctypes.data, int(cam), n, lm.ctypes.data if n else None,
+                                                          ft.ctypes.data if n else None, xy.ctypes.data if n else None,
+                                                          float(max_err), st.ctypes.data, C.byref(added)))
+        return st[:n], added.value
+
     def remove_outliers(self):
         npts = self.counts()[1]
         new_idx = np.zeros(max(1, npts), np.int32)

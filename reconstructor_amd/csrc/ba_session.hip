@@ -430,4 +430,55 @@ int rcn_ba_session_triangulate(rcn_ba_session *s, const double *poses34_host, in
     return RCN_OK;
 }
 
+// step 1 of triangulateMatchedLandmarks (:497-512) against the session's landmarks (corr2d3d.hip): the points never leave
+// HBM, the status bytes come back, and the attached entries are appended to their tracks in list order -- exactly what
+// rcn_ba_session_add_observations of those entries does.
+int rcn_ba_session_attach(rcn_ba_session *s, const double *poses34_host, int32_t cam, int32_t n, const int32_t *landmark,
+                          const int32_t *feat, const int32_t *xy, double max_projection_error, uint8_t *status_out, int32_t *n_added_out)
+{
+    if (!s || !poses34_host || n < 0 || (n > 0 && (!landmark || !feat || !xy))) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (n_added_out) *n_added_out = 0;
+    if (cam < 0 || cam >= nc) { ctx->set_error("rcn_ba_session_attach: camera index out of range"); return RCN_ERR_ARG; }
+    int32_t n_feat = 0;
+    int rc = rcn_int_attach_check(ctx, "rcn_ba_session_attach", np, n, landmark, feat, &n_feat);
+    if (rc) return rc;
+    if (n == 0) return RCN_OK;
+    SES_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_e = al(4 * (size_t)n);
+    SES_HIP(ctx->att_ws.reserve(256 + 4 * b_e + al((size_t)n) + rcn_int_attach_ws_bytes(n_feat)));
+    char *w = ctx->att_ws.as<char>();
+    double *d_P = reinterpret_cast<double *>(w), *d_K = reinterpret_cast<double *>(w + 128);
+    int32_t *d_lm = reinterpret_cast<int32_t *>(w + 256), *d_ft = reinterpret_cast<int32_t *>(w + 256 + b_e),
+            *d_xy = reinterpret_cast<int32_t *>(w + 256 + 2 * b_e);
+    uint8_t *d_st = reinterpret_cast<uint8_t *>(w + 256 + 4 * b_e);
+    void *d_ws = w + 256 + 4 * b_e + al((size_t)n);
+    SES_HIP(hipMemcpyAsync(d_P, poses34_host + 12 * (size_t)cam, 96, hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(d_K, s->intr.data() + 6 * (size_t)cam, 48, hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(d_lm, landmark, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(d_ft, feat, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(d_xy, xy, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    rc = rcn_int_attach_launch(ctx, d_P, d_K, static_cast<const double *>(s->pts.p), np, n, d_lm, d_ft, d_xy, n_feat,
+                               max_projection_error, d_st, d_ws);
+    if (rc) return rc;
+    std::vector<uint8_t> status((size_t)n);
+    SES_HIP(hipMemcpyAsync(status.data(), d_st, (size_t)n, hipMemcpyDeviceToHost, st));
+    SES_HIP(hipStreamSynchronize(st));
+    int32_t added = 0;
+    for (int32_t e = 0; e < n; ++e) {
+        if (status[e] != 0) continue;
+        s->tracks[landmark[e]].push_back(TrackObs{cam, xy[2 * (size_t)e], xy[2 * (size_t)e + 1]});     // triangulatedFeatures.push_back
+        ++added;
+    }
+    s->n_obs += added;
+    if (added) { s->obs_dirty = true; s->have_inlier = false; ++s->version; }
+    if (status_out) std::copy(status.begin(), status.end(), status_out);
+    if (n_added_out) *n_added_out = added;
+    return RCN_OK;
+}
+
 }  // extern "C"

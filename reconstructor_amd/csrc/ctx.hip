@@ -12,9 +12,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.4 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.5 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.4 (gfx950)";
+    return "reconstructor_amd 0.5 (gfx950)";
 #endif
 }
 
@@ -206,6 +206,9 @@ void rcn_destroy(rcn_ctx *ctx)
     ctx->fm_state.release();
     ctx->fm_csr.release(); ctx->fm_pairs.release();
     for (auto &kv : ctx->coords) kv.second.first.release();
+    ctx->corr.release();
+    ctx->corr_ws.release(); ctx->corr_hws.release(); ctx->corr_slots.release(); ctx->att_ws.release();
+    if (ctx->corr_ev) (void)hipEventDestroy(ctx->corr_ev);
     if (ctx->ev_made) {
         for (auto &call : ctx->ev_c)
             for (auto &row : call)

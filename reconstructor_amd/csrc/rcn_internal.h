@@ -106,6 +106,18 @@ struct ScaleDev {
 // fused table filter (fmat.hip): per-pair keypoint coordinate lists
 struct PairXY { const int32_t *q, *t; int32_t Kq, pad; };
 
+// 2D-3D correspondence search (corr2d3d.hip): the directed match lists of rcn_match_lists_upload, resident in HBM
+struct CorrLists {
+    bool live = false, mirror = false;
+    std::vector<int32_t> ids;         // slot -> image id, ascending: the images of the lists
+    int32_t id_lo = 0, id_span = 0;   // id2slot covers ids id_lo .. id_lo + id_span - 1
+    DevBuf ent;                       // (feature of a, feature of b) per entry, pair by pair
+    DevBuf list_off;                  // int64, n_pairs + 1
+    DevBuf dir;                       // n_slots x n_slots int32: (list << 1) | read backwards (mirror), -1 = no list
+    DevBuf id2slot;                   // int32, -1 = not in the lists
+    void release() { ent.release(); list_off.release(); dir.release(); id2slot.release(); ids.clear(); live = false; id_lo = id_span = 0; }
+};
+
 struct rcn_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -184,6 +196,12 @@ struct rcn_ctx {
     std::vector<PairXY> fm_pairs_host;   // staging of fm_pairs (uploaded asynchronously)
     DevBuf fm_csr, fm_pairs;   // fused table filter: CSR of the matched points, per-pair coordinate pointers
     std::map<int32_t, std::pair<DevBuf, int32_t>> coords;   // image id -> (K x 2 int32 pixel coordinates in HBM, K)
+    CorrLists corr;                     // corr2d3d.hip: resident match lists
+    DevBuf corr_ws, corr_hws, corr_slots, att_ws;   // ... workspace (obs_of, hit rows, tile counts), host-API staging, slot table, attach staging
+    std::vector<char> corr_slots_host;  // staging of corr_slots (uploaded asynchronously; corr_ev marks the copy)
+    hipEvent_t corr_ev = nullptr;
+    bool corr_slots_pending = false;
+    int64_t corr_budget = 1ll << 30;    // bytes of hit rows per batch (rcn_corr_set_workspace_bytes)
     std::vector<int> ba_graph_cam, ba_graph_pt;     // observation graph of the last plain rcn_ba_solve (host copy): an identical graph reuses the pair lists
     int ba_graph_nc = 0, ba_graph_np = 0;
     uint64_t ba_graph_serial = 0;
@@ -259,6 +277,12 @@ int rcn_int_triangulate_check(rcn_ctx *ctx, int32_t n_cams, int32_t n_tracks, in
 size_t rcn_int_triangulate_ws_bytes(int32_t n_cams, int32_t n_tracks);
 int rcn_int_triangulate_launch(rcn_ctx *ctx, const rcn_triangulation_problem *dp, double max_err, double min_angle, void *ws,
                                double *xyz, uint8_t *status, double *compact, int32_t compact_first, int32_t *n_accepted);
+// corr2d3d.hip, with ctx->mu held: step 1 of triangulateMatchedLandmarks on device arrays (rcn_ba_session_attach)
+int rcn_int_attach_check(rcn_ctx *ctx, const char *who, int32_t n_points, int32_t n, const int32_t *lm, const int32_t *feat, int32_t *n_feat);
+size_t rcn_int_attach_ws_bytes(int32_t n_feat);
+int rcn_int_attach_launch(rcn_ctx *ctx, const double *P, const double *K, const double *pts, int32_t n_points, int32_t n,
+                          const int32_t *lm, const int32_t *feat, const int32_t *xy, int32_t n_feat, double max_err,
+                          uint8_t *status, void *ws);
 // store.hip: rcn_match_compact_begin / _wait with ctx->mu already held
 int rcn_int_compact_begin(rcn_ctx *ctx, const int32_t *table_dev, int64_t stride, const int32_t *counts_dev,
                           int32_t n_pairs, int64_t *offsets_host, int32_t *qt_host, int64_t capacity, int64_t *total_out);

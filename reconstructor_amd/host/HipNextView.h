@@ -1,0 +1,174 @@
+// HipNextView.h -- SequentialReconstructor::calc2d3dMatches, ::rankNextImages and step 1 of ::triangulateMatchedLandmarks
+// (SequentialReconstructor.cpp:643-695, :697-759, :497-512) over the reference's own containers, with the search handed to
+// rcn_corr_2d3d and the attach rules to rcn_landmark_attach (include/rcn.h).
+//   uploadMatches     once per reconstruction: every image's keypoint coordinates and the lists featureMatches[(i, c)] for
+//                     which i is in imgMatches[c] (calc2d3dMatches' own condition), as given (no mirror)
+//   calc2d3dMatches   the reference's signature plus the containers it reads; fills imgIdToLandmarkIds /
+//                     imgIdToFeatureIds per candidate in the reference's order.  Throws if a candidate feature already has
+//                     a landmark (the reference skips it; in its flow an unregistered image has none, and the device search
+//                     does not model the test).
+//   rankNextImages    the reference's own ranking code and containers (std::map keyed by score / image id) over the scores
+//                     the last calc2d3dMatches computed on the GPU: both modes and their ties exactly as the reference.
+//   attachMatchedLandmarks  step 1: rcn_landmark_attach, then push_back / landmarkId in list order.
+#pragma once
+#include <algorithm>
+#include <functional>
+#include <map>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/rcn.h"
+#include "rcn_types.h"
+
+namespace reconstructor::Core {
+
+enum NextImageRankingMode { MatchTotal = 0, MatchDensity = 1 };      // SequentialReconstructor.h:45
+
+class NextViewSearch {
+public:
+    explicit NextViewSearch(rcn_ctx *ctx = nullptr) : ctx_(ctx), owned_(false)
+    {
+        if (!ctx_) {
+            if (rcn_create(0, &ctx_) != RCN_OK) throw std::runtime_error("NextViewSearch: no usable gfx950 device");
+            owned_ = true;
+        }
+    }
+    ~NextViewSearch() { if (owned_) rcn_destroy(ctx_); }
+    NextViewSearch(const NextViewSearch &) = delete;
+    NextViewSearch &operator=(const NextViewSearch &) = delete;
+
+    NextImageRankingMode nextImageRankingMode = MatchDensity;   // SequentialReconstructor.h:237
+    int min2d3dMatchNum = 30;                                   // SequentialReconstructor.h:240
+    double maxProjectionError = 4.0;                            // SequentialReconstructor.h:256
+
+    template <class FeatureMatches>
+    void uploadMatches(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                       std::unordered_map<int, std::vector<int>> &imgMatches, FeatureMatches &featureMatches)
+    {
+        for (const auto &[imgIdx, feats] : features) {
+            std::vector<int32_t> xy;
+            for (const auto &f : feats) { xy.push_back(f->featCoord.x); xy.push_back(f->featCoord.y); }
+            check(rcn_coords_upload(ctx_, imgIdx, xy.empty() ? nullptr : xy.data(), (int32_t)feats.size()), "rcn_coords_upload");
+        }
+        std::vector<int32_t> pairs, qt;
+        std::vector<int64_t> offsets{0};
+        for (const auto &[key, m] : featureMatches) {
+            const auto &cm = imgMatches[key.second];
+            if (m.empty() || std::find(cm.begin(), cm.end(), key.first) == cm.end()) continue;
+            pairs.push_back(key.first); pairs.push_back(key.second);
+            for (const auto &[f, g] : m) { qt.push_back(f); qt.push_back(g); }
+            offsets.push_back((int64_t)qt.size() / 2);
+        }
+        check(rcn_match_lists_upload(ctx_, (int32_t)(pairs.size() / 2), pairs.data(), offsets.data(), qt.empty() ? nullptr : qt.data(), 0),
+              "rcn_match_lists_upload");
+    }
+
+    void calc2d3dMatches(const std::set<int> &candidateImgIds, std::unordered_map<int, std::vector<int>> &imgIdToLandmarkIds,
+                         std::unordered_map<int, std::vector<int>> &imgIdToFeatureIds,
+                         std::unordered_map<int, std::vector<FeaturePtr<>>> &features, const std::vector<Landmark> &landmarks,
+                         std::unordered_map<int, std::pair<int, int>> &imgIdx2imgShape)
+    {
+        std::vector<int32_t> off{0}, img, feat, cand, shape;
+        for (const auto &lm : landmarks) {
+            for (const auto &tf : lm.triangulatedFeatures) { img.push_back(tf.imgIdx); feat.push_back(tf.featIdx); }
+            off.push_back((int32_t)img.size());
+        }
+        for (int c : candidateImgIds) {
+            cand.push_back(c);
+            const auto &s = imgIdx2imgShape.at(c);
+            shape.push_back(s.first); shape.push_back(s.second);
+        }
+        const size_t n = cand.size();
+        std::vector<int64_t> coff(n + 1);
+        std::vector<int32_t> cells(n + 1), lid, fid;
+        int64_t total = 0, cap = (int64_t)std::min<size_t>(img.size() * std::max<size_t>(n, 1), 1u << 20) + 1;
+        for (int attempt = 0;; ++attempt) {
+            lid.resize(cap); fid.resize(cap);
+            const int rc = rcn_corr_2d3d(ctx_, (int32_t)landmarks.size(), off.data(), img.data(), feat.data(), (int32_t)n, cand.data(),
+                                         shape.data(), coff.data(), lid.data(), fid.data(), cap, &total, cells.data(), nullptr);
+            if (rc == RCN_OK) break;
+            if (attempt || total <= cap) check(rc, "rcn_corr_2d3d");
+            cap = total;
+        }
+        lastScore_.clear();
+        for (size_t k = 0; k < n; ++k) {
+            const int c = cand[k];
+            std::vector<int> L(lid.begin() + coff[k], lid.begin() + coff[k + 1]), F(fid.begin() + coff[k], fid.begin() + coff[k + 1]);
+            for (int g : F)
+                if (features.at(c).at(g)->landmarkId != -1)
+                    throw std::runtime_error("calc2d3dMatches: feature " + std::to_string(g) + " of candidate " + std::to_string(c) +
+                                             " already has a landmark");
+            imgIdToLandmarkIds[c] = std::move(L);
+            imgIdToFeatureIds[c] = std::move(F);
+            lastScore_[c] = cells[k];
+        }
+    }
+
+    // :697-759 with projDensity.sum() replaced by the GPU's count of occupied cells
+    void rankNextImages(const std::unordered_map<int, std::vector<int>> &imgIdToLandmarkIds,
+                        const std::unordered_map<int, std::vector<int>> &imgIdToFeatureIds, std::vector<int> &candidateImgIdsSorted)
+    {
+        if (nextImageRankingMode == MatchTotal) {
+            std::map<int, int, std::greater<int>> imgId2NumMatches;
+            for (const auto &[imgId, landmarkIds] : imgIdToLandmarkIds) imgId2NumMatches[imgId] = (int)landmarkIds.size();
+            for (const auto &[imgId, numMatches] : imgId2NumMatches) candidateImgIdsSorted.push_back(imgId);
+        } else if (nextImageRankingMode == MatchDensity) {
+            std::map<int, int, std::greater<int>> score2imgId;
+            for (const auto &[imgId, featIds] : imgIdToFeatureIds) score2imgId[lastScore_.at(imgId)] = imgId;
+            for (const auto &[score, imgId] : score2imgId)
+                if (score > min2d3dMatchNum) candidateImgIdsSorted.push_back(imgId);
+        } else {
+            throw std::runtime_error("Wrong next image ranking mode!");
+        }
+    }
+
+    // step 1 of triangulateMatchedLandmarks (:497-512).  Returns the status per entry (0 attached, 1 depth,
+    // 2 reprojection, 3 feature already taken).
+    template <class Pose4>
+    std::vector<uint8_t> attachMatchedLandmarks(int imgIdx, const std::vector<int> &featureIds, const std::vector<int> &landmarkIds,
+                                                std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                                                std::vector<Landmark> &landmarks, std::unordered_map<int, Pose4> &imgIdx2camPose,
+                                                std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics)
+    {
+        const size_t n = featureIds.size();
+        std::vector<uint8_t> status(n + 1);
+        if (n == 0) { status.resize(0); return status; }
+        double P[12], K[6];
+        const Pose4 &T = imgIdx2camPose.at(imgIdx);
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) P[4 * r + c] = T(r, c);
+        const PinholeCamera &k = imgIdx2camIntrinsics.at(imgIdx);
+        K[0] = k.fX; K[1] = k.fY; K[2] = k.cX; K[3] = k.cY; K[4] = k.k1; K[5] = k.k2;
+        std::vector<double> pts;
+        pts.reserve(3 * landmarks.size() + 3);
+        for (const auto &lm : landmarks) { pts.push_back(lm.x); pts.push_back(lm.y); pts.push_back(lm.z); }
+        std::vector<int32_t> xy;
+        for (int f : featureIds) { xy.push_back(features.at(imgIdx).at(f)->featCoord.x); xy.push_back(features.at(imgIdx).at(f)->featCoord.y); }
+        std::vector<int32_t> lid(landmarkIds.begin(), landmarkIds.end()), fid(featureIds.begin(), featureIds.end());
+        check(rcn_landmark_attach(ctx_, P, K, (int32_t)landmarks.size(), pts.data(), (int32_t)n, lid.data(), fid.data(), xy.data(),
+                                  maxProjectionError, status.data(), nullptr), "rcn_landmark_attach");
+        status.resize(n);
+        for (size_t e = 0; e < n; ++e) {
+            if (status[e] != 0) continue;
+            if (features[imgIdx][featureIds[e]]->landmarkId != -1)
+                throw std::runtime_error("attachMatchedLandmarks: feature already has a landmark");
+            landmarks[landmarkIds[e]].triangulatedFeatures.emplace_back(imgIdx, featureIds[e]);
+            features[imgIdx][featureIds[e]]->landmarkId = landmarkIds[e];
+        }
+        return status;
+    }
+
+private:
+    void check(int rc, const char *what)
+    {
+        if (rc != RCN_OK) throw std::runtime_error(std::string(what) + ": " + rcn_last_error(ctx_));
+    }
+    rcn_ctx *ctx_;
+    bool owned_;
+    std::unordered_map<int, int> lastScore_;
+};
+
+}  // namespace reconstructor::Core
