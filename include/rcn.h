@@ -47,9 +47,9 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * its arguments: a caller built against an older header must not be linked against a newer library (rcn_match_last_stats copies the whole
  * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
- * correspondence search and the attach entry points).
+ * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 5
+#define RCN_ABI_REVISION 6
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -162,6 +162,9 @@ typedef struct {
     int64_t rows_brute_force;     /* of rows_exact_fallback: rows that went through K2b after all (candidate list overflowed, budget exceeded, D % 4 != 0) */
     int32_t chunks;               /* pipeline chunks of the last grid call (candidate table / row lists are sized per chunk) */
     int32_t coarse_launches;      /* coarse-kernel launches summed into coarse_ms (chunks x profiled calls) */
+    int32_t coarse_dtype;         /* number format of the coarse pass of the last grid call: 0 none (exact kernels only), 1 fp16 MFMA, 2 int8 MFMA
+                                   * (D padded to 256, at most 4096 padded rows per image, rows not peaked: DESIGN.md section 5) */
+    int32_t reserved0;
 } rcn_match_stats;
 int rcn_match_last_stats(const rcn_ctx *ctx, rcn_match_stats *out);
 /* enable != 0: bracket the kernels of every following grid call with HIP events on the ctx

@@ -51,7 +51,8 @@ class MatchStats(C.Structure):
                 ("pair_distances", C.c_int64), ("err_bound_d2", C.c_double),
                 ("used_mfma_path", C.c_int32), ("profiled_calls", C.c_int32),
                 ("coarse_ms", C.c_double), ("rerank_ms", C.c_double), ("unique_ms", C.c_double),
-                ("rows_brute_force", C.c_int64), ("chunks", C.c_int32), ("coarse_launches", C.c_int32)]
+                ("rows_brute_force", C.c_int64), ("chunks", C.c_int32), ("coarse_launches", C.c_int32),
+                ("coarse_dtype", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ShardStats(C.Structure):

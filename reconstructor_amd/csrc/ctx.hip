@@ -12,9 +12,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.5 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.6 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.5 (gfx950)";
+    return "reconstructor_amd 0.6 (gfx950)";
 #endif
 }
 
@@ -115,6 +115,10 @@ int rcn_create(int device_id, rcn_ctx **out)
     ctx->coarse_w4 = w4 && w4[0] == '1';
     const char *s16 = std::getenv("RCN_COARSE_S16");
     ctx->coarse_shape = s16 ? (s16[0] == '1' ? 1 : 0) : -1;
+    const char *i8 = std::getenv("RCN_COARSE_I8");
+    ctx->coarse_i8_off = i8 && i8[0] == '0';
+    const char *i8s = std::getenv("RCN_COARSE_I8_S16");
+    ctx->coarse_i8_shape = i8s ? (i8s[0] == '1' ? 1 : 0) : -1;
     const char *fe = std::getenv("RCN_FORCE_EXACT");
     ctx->force_exact = fe && fe[0] == '1';
     const char *nio = getenv("RCN_MATCH_NO_ORDER");

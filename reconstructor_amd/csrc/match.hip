@@ -35,6 +35,14 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                                      // setting) 3116 ms, 6.2 GB; 31 chunks 3135 ms, 4.4 GB
 #define RCN_BT 64           // train rows per LDS tile (k_coarse_w4; k_coarse_top2: coarse_bt)
 #define RCN_PAD_HN 1.0e30f  // half-norm of padded train rows: never a candidate
+// int8 coarse pass (D padded to 256, Kp <= 4096; coarse_i8.h)
+#define RCN_I8_IDX_BITS 12                              // train-row bits of an int8 key
+#define RCN_I8_IDX_MASK ((1u << RCN_I8_IDX_BITS) - 1u)
+#define RCN_I8_PAD_ACC ((1 << (32 - RCN_I8_IDX_BITS)) - 1)   // accumulator of a padded train row: ranks last, fits the key
+#define RCN_I8_BT 128                                   // train rows per LDS tile
+#define RCN_I8_RES_MAX 8.01                             // |s x - xq| <= sqrt(256) / 2 for a row inside the grid, with room for its rounding up
+#define RCN_I8_M_MAX 720.0                              // largest s Nmax + 8.5 for which every accumulator fits the key (fix_scale)
+#define RCN_I8_PEAK_MAX 8.0                             // int8 only when max |x| sqrt(D) / Nmax is below this (fix_scale)
 
 // ---------------------------------------------------------------------------------------
 // 16-byte-chunk swizzle of the fp16 image.  A row of DP halfs has DP/8 chunks; rows that a
@@ -147,6 +155,7 @@ __global__ void k_prepare(const float *__restrict__ x, const double *__restrict_
                           _Float16 *__restrict__ f16, float *__restrict__ hn, unsigned long long *__restrict__ bigmin)
 {
     constexpr int CPR = DP / 8;
+    if (sc->coarse_i8) return;           // the resident set holds int8 copies (k_prepare_i8)
     const float scale = sc->sf;
     const double half_s2 = sc->hs2, bias = sc->bias, thr2 = sc->thr2;
     int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -186,6 +195,7 @@ __global__ void k_prepare_batch(const float *__restrict__ x, const double *__res
 {
     // every image owns a slot of Kslot fp32 rows; Ks (may be NULL = Kslot everywhere) holds the rows in use
     constexpr int CPR = DP / 8;
+    if (sc->coarse_i8) return;           // the resident set holds int8 copies (k_prepare_i8)
     const float scale = sc->sf;
     const double half_s2 = sc->hs2, bias = sc->bias, thr2 = sc->thr2;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -219,6 +229,72 @@ __global__ void k_prepare_batch(const float *__restrict__ x, const double *__res
     if (c == 0) hn[grow] = (row < K && !big) ? (float)(half_s2 * n2 + bias) : RCN_PAD_HN;
 }
 
+// int8 path (D padded to 256; fix_scale set ScaleDev::coarse_i8): fp32 rows of n equally shaped images -> int8 rows
+// xq = rint(s x) in [-127, 127] (256 bytes, sixteen 16-byte chunks, chunk c of row r at slot c ^ (r & 15)), integer half-norms
+// rint(s^2 |x|^2 / 2) + BIAS, and per row the two norms the certificates need, in fp64 from the fp32 input and rounded UP:
+//   |xq|       exact integer sum of squares, then sqrt
+//   |s x - xq| the residual the accumulator does not see.  s x is an fp64 product of an fp32 and an fp64 number: relative error
+//              2^-53 on a value of at most 127, i.e. below 1.5e-14 per element and 2.3e-13 on the norm; the 1e-6 added below covers
+//              that, the sqrt, the sum and the conversion to fp32 with five orders of magnitude to spare.
+// img_stride: bytes between two images' copies (an image of a slab keeps the place of its fp16 copy and uses the first half of it).
+// Sixteen consecutive threads convert one row (one chunk each) and reduce the two sums by shuffles.  imax: counters words
+// RCN_I8_WORD / + 1, the running maxima of |s x - xq| and |xq| (non-negative floats order like their bit patterns).
+// A row whose norm is not finite (a NaN element) is never anybody's neighbour in the canonical matcher: it gets the padding
+// treatment (zeros, accumulator 2^20 - 1) and does not count towards the maxima; as a QUERY it goes to the exact kernel (k_filter).
+__global__ __launch_bounds__(256) void k_prepare_i8(const float *__restrict__ x, const double *__restrict__ nrm2,
+                                                    int n, int Kslot, int Kp, int D, const ScaleDev *__restrict__ sc,
+                                                    signed char *__restrict__ i8, long img_stride, int *__restrict__ hn, float2 *__restrict__ i8n,
+                                                    const int32_t *__restrict__ Ks, unsigned long long *__restrict__ bigmin,
+                                                    unsigned *__restrict__ imax)
+{
+    if (!sc->coarse_i8) return;
+    const double s = sc->s, half_s2 = sc->hs2, bias = sc->bias;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long grow = gid >> 4;
+    const int c = (int)(gid & 15);
+    if (grow >= (long)n * Kp) return;            // (whole rows leave together: 16 threads per row, 256 per workgroup)
+    const int img = (int)(grow / Kp), row = (int)(grow % Kp);
+    const float *xi = x + (size_t)img * Kslot * D;
+    const int K = Ks ? Ks[img] : Kslot;
+    const double n2 = row < K ? nrm2[(size_t)img * Kslot + row] : 0.0;
+    const bool live = row < K && n2 <= 1.7976931348623157e308;      // false for a NaN / infinite norm
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+    double sq = 0.0, sr = 0.0;
+    if (live) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int k = c * 16 + e;
+            const double v = k < D ? (double)xi[(size_t)row * D + k] * s : 0.0;
+            double qd = rint(v);
+            qd = qd > 127.0 ? 127.0 : (qd < -127.0 ? -127.0 : qd);
+            const double r = v - qd;
+            sq = fma(qd, qd, sq);
+            sr = fma(r, r, sr);
+            w[e >> 2] |= ((unsigned)(int)qd & 0xFFu) << (8 * (e & 3));
+        }
+    }
+    *reinterpret_cast<uint4 *>(i8 + (size_t)img * img_stride + (size_t)row * 256 + ((c ^ (row & 15)) << 4)) = make_uint4(w[0], w[1], w[2], w[3]);
+    for (int o = 8; o; o >>= 1) { sq += __shfl_xor(sq, o); sr += __shfl_xor(sr, o); }
+    if (c == 0) {
+        hn[grow] = live ? (int)(rint(half_s2 * n2) + bias) : RCN_I8_PAD_ACC;
+        const float qn = live ? __double2float_ru(sqrt(sq) * (1.0 + 1e-9)) : 0.f;
+        const float rn = live ? __double2float_ru(sqrt(sr) * (1.0 + 1e-9) + 1.0e-6) : 0.f;
+        i8n[grow] = make_float2(qn, rn);
+        if (live) {
+            if (__float_as_uint(rn) > __hip_atomic_load(imax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(imax, __float_as_uint(rn));
+            if (__float_as_uint(qn) > __hip_atomic_load(imax + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(imax + 1, __float_as_uint(qn));
+        }
+        if (row == 0) bigmin[img] = 0x7FF0000000000000ull;       // no BIG rows on this path
+    }
+}
+// (one thread, behind the conversions) the maxima into the scale record, with room for the fp32 -> fp64 step being exact anyway
+__global__ void k_i8_commit(const unsigned *__restrict__ imax, ScaleDev *__restrict__ sc)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    sc->rho = (double)__uint_as_float(imax[0]);
+    sc->tau = (double)__uint_as_float(imax[1]);
+}
+
 // +infinity (as bits) into n words: "no BIG row" before a conversion records any
 __global__ void k_fill_inf(unsigned long long *p, int n)
 {
@@ -238,8 +314,12 @@ __global__ void k_fill_inf(unsigned long long *p, int n)
 // other query's certificates through their smallest norm (k_filter) -- and the scale is fixed for the rows below:
 // o->thr2 = 2^(top normal octave + 1), s from sqrt(thr2), |x|^2 bound = thr2.  Without such a split thr2 = +infinity and
 // everything is as it was (same s, same BIAS, bit for bit).
-__host__ __device__ inline void fix_scale(float maxabs, double maxn2, const unsigned *hist, int DPa, ScaleDev *o)
+// allow_i8: the host-known preconditions of the int8 coarse pass hold (DPa == 256, every resident image has at most 4096 padded rows,
+// no diagnostic switch against it).  The data decide the rest here, on the device or on the host alike (see the end of the function).
+__host__ __device__ inline void fix_scale(float maxabs, double maxn2, const unsigned *hist, int DPa, int allow_i8, ScaleDev *o)
 {
+    const bool stats_ok = maxabs > 0.f && maxabs <= 3.4028234e38f && maxn2 > 0.0 && maxn2 <= 1.7976931348623157e308;
+    const float maxabs_in = maxabs;
     if (!(maxabs > 0.f && maxabs <= 3.4028234e38f)) maxabs = 1.f;          // zero, NaN, infinity
     if (!(maxn2 > 0.0 && maxn2 <= 1.7976931348623157e308)) maxn2 = 1.0;
     double thr2 = 1.0e308 * 10.0;                                            // +infinity
@@ -281,13 +361,49 @@ __host__ __device__ inline void fix_scale(float maxabs, double maxn2, const unsi
     o->rel_slack = 1e-9;
     o->thr2 = thr2;
     o->sf = (float)s; o->pad = 0.f;
+    o->rho = 0.0; o->tau = 0.0; o->coarse_i8 = 0; o->pad2 = 0;
+    // ---- int8 coarse pass.  Chosen when
+    //   * the host-known preconditions hold, the statistics are finite and no BIG-row split is in force, and
+    //   * the rows are not peaked: P = max |x| sqrt(D) / Nmax < RCN_I8_PEAK_MAX.  A uniform grid over [-max |x|, max |x|] resolves a row
+    //     of norm N with step max |x| / 127, i.e. N / (step sqrt(D)) = 127 / P steps per rms element.  Unit-norm rows of near-Gaussian
+    //     elements (SuperPoint, the benchmark) have P about 6 (the maximum of 1e9 Gaussians is 6.1 sigma) and 21 steps per rms element:
+    //     the CPU emulation (tests/test_int8_emulation.py) certifies 98.8 % of such rows from the coarse pair.  At P = 8 it is 16 steps;
+    //     heavy-tailed rows (Laplace 13+, Student-t and one huge element far more) and integer-valued descriptors whose rows differ in
+    //     norm lie above and keep the fp16 pass, which is today's behaviour exactly.  Whatever is chosen, results do not change: the
+    //     certificates price the residual of every row exactly.
+    // Scale: s = min(127 / max |x|, (RCN_I8_M_MAX - 8.5) / Nmax), max |x| rounded up to a 1/32-octave grid like the norm bound so that the
+    // scale stays put while images of similar range come and go.  With M = s Nmax + 8.5 every quantised row has |xq| <= s |x| + |r| <= M
+    // (|r| <= 8 + rounding), and for every pair of resident rows
+    //     acc = rint(s^2 |t|^2 / 2) + BIAS - qq.tq,   qq.tq <= |qq| |tq| <= M (s |t| + RCN_I8_RES_MAX),
+    //     s^2 |t|^2 / 2 - M s |t| >= -M^2 / 2   =>   acc >= BIAS - 0.5 - M^2 / 2 - RCN_I8_RES_MAX M  >= 1   with
+    //     BIAS = ceil(M^2 / 2 + RCN_I8_RES_MAX M) + 2,   and
+    //     acc <= s^2 Nmax^2 / 2 + 0.5 + BIAS + M^2 <= 2 M^2 + RCN_I8_RES_MAX M + 4 <= 1 042 572 < 2^20 - 1 = RCN_I8_PAD_ACC   for M <= 720:
+    // the key (acc << 12 | row) neither wraps nor reaches a padded row's.  (tests/test_int8_gpu.py: rows whose elements all equal the maximum.)
+    if (allow_i8 && DPa == 256 && stats_ok && !(thr2 <= 1.7976931348623157e308)) {
+        int ea;
+        const double ma = frexp((double)maxabs_in * (1.0 + 1e-12), &ea);
+        const double maxabs_q = ldexp(ceil(ma * 64.0) / 64.0, ea);
+        const double peak = maxabs_q * 16.0 / n_max;
+        if (peak < RCN_I8_PEAK_MAX) {
+            double s8 = 127.0 / maxabs_q;
+            const double cap = (RCN_I8_M_MAX - 8.5) / n_max;
+            if (s8 > cap) s8 = cap;
+            const double M = s8 * n_max + 8.5;
+            const double bias8 = ceil(0.5 * M * M + RCN_I8_RES_MAX * M) + 2.0;
+            o->s = s8; o->s2 = s8 * s8; o->hs2 = 0.5 * s8 * s8; o->bias = bias8;
+            o->c_in = 0.0; o->c_sub = 0.0; o->c_acc = 0.0;
+            o->hn_max = 0.5 * s8 * s8 * n_max * n_max + 0.5 + bias8;
+            o->sf = (float)s8;
+            o->coarse_i8 = 1;
+        }
+    }
 }
-__global__ void k_fix_scale(const unsigned *__restrict__ counters, int DPa, ScaleDev *__restrict__ out)
+__global__ void k_fix_scale(const unsigned *__restrict__ counters, int DPa, int allow_i8, ScaleDev *__restrict__ out)
 {
     if (threadIdx.x || blockIdx.x) return;
     const float maxabs = __uint_as_float(counters[0]);
     const double maxn2 = __longlong_as_double(*reinterpret_cast<const long long *>(counters + 2));
-    fix_scale(maxabs, maxn2, counters + RCN_HIST_WORD, DPa, out);
+    fix_scale(maxabs, maxn2, counters + RCN_HIST_WORD, DPa, allow_i8, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -308,9 +424,11 @@ struct CoarseArgs {
     uint2 *cand;            // [n_pairs][kq_stride] packed (best, second)
     int32_t n_groups, tiles_per_pair, items_per_xcd, kq_stride;
     uint32_t idx_mask;      // low bits that carry the train row
+    const ScaleDev *sc;     // the launch belongs to the fp16 kernels unless sc->coarse_i8 (then to k_coarse_top2_i8): the other one returns at once
 };
 
 #include "coarse_w4.h"
+#include "coarse_i8.h"
 
 // K1: one workgroup (8 waves, 2 per SIMD) = 512 query rows of one image against every train row
 //   of up to RCN_GROUP consecutive pairs that share that query image; query fragments are
@@ -354,6 +472,7 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2(CoarseArgs a)
     constexpr int BUFB = TILEB + 8 * BT * 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
+    if (DP == 256 && a.sc->coarse_i8) return;                // the resident set holds int8 copies: k_coarse_top2_i8's launch
     const int b = blockIdx.x;
     const int item = (b & 7) * a.items_per_xcd + (b >> 3);  // XCD x walks a contiguous item range
     if (item >= a.n_groups * a.tiles_per_pair) return;
@@ -741,6 +860,38 @@ __device__ __forceinline__ double acc_to_d2(const ScaleDev &a, double nq2, doubl
     return nq2 + (2.0 / a.s2) * (acc - a.bias);
 }
 
+// ---- the two key formats behind one reading (S.coarse_i8 is uniform over a launch) ---------------------------------------
+// fp16 path: the key is the fp32 accumulator with the train row in its low idx bits -- the value lies in [lo, hi) with hi one
+// quantum above lo.  int8 path: key = acc << 12 | row, the accumulator is an exact integer and lo = hi.
+__device__ __forceinline__ double key_lo(const ScaleDev &S, unsigned k, uint32_t mask)
+{
+    return S.coarse_i8 ? (double)(k >> RCN_I8_IDX_BITS) : (double)__uint_as_float(k & ~mask);
+}
+__device__ __forceinline__ double key_hi(const ScaleDev &S, unsigned k, uint32_t mask)
+{
+    return S.coarse_i8 ? (double)(k >> RCN_I8_IDX_BITS) : (double)__uint_as_float((k & ~mask) + mask + 1u);
+}
+// a padding / BIG row's key: its accumulator says nothing about a distance
+__device__ __forceinline__ bool key_is_pad(const ScaleDev &S, unsigned k, uint32_t mask)
+{
+    return S.coarse_i8 ? (k >> RCN_I8_IDX_BITS) >= (unsigned)RCN_I8_PAD_ACC : !(__uint_as_float(k & ~mask) < 1.0e29f);
+}
+__device__ __forceinline__ int key_idx(const ScaleDev &S, unsigned k, uint32_t mask)
+{
+    return (int)(k & (S.coarse_i8 ? RCN_I8_IDX_MASK : mask));
+}
+// coarse-error bound for query row q of image qi, accumulator units.  int8 path: with qq, tq the quantised rows and rq, rt the
+// residuals s q - qq, s t - tq,  s^2 q.t - qq.tq = qq.rt + rq.tq + rq.rt, so by Cauchy-Schwarz with the row's own exact norms and the
+// maxima rho >= |rt|, tau >= |tq| over every converted row
+//     |acc - (s^2 |t|^2 / 2 - s^2 q.t + BIAS)| <= |qq| rho + |rq| tau + |rq| rho + 0.5      (0.5: the rounding of the integer half-norm)
+// -- nothing else: the integer accumulation is exact.  (1e-3 on top: the fp64 evaluation of half_s2 * |t|^2 before its rounding, and of this sum.)
+__device__ __forceinline__ double coarse_eps_row(const ScaleDev &S, const ImgDev &qi, int q, double nq2)
+{
+    if (!S.coarse_i8) return coarse_eps(S, nq2);
+    const float2 n = qi.i8n[q];
+    return ((double)n.x * S.rho + (double)n.y * (S.tau + S.rho)) * (1.0 + 1e-9) + 0.5 + 1.0e-3;
+}
+
 // lower bound on the exact squared distance from a query of squared norm nq2 to ANY BIG row of an image: (|t| - |q|)^2 with
 // |t| >= the image's smallest BIG norm, evaluated with a relative slack; +infinity when the image has no BIG row
 __device__ __forceinline__ double big_lower_bound(const unsigned long long *bigmin, double nq2)
@@ -805,15 +956,15 @@ __global__ __launch_bounds__(RCN_FT) void k_filter(RerankArgs a)
                 const uint2 c = cv[r];
                 // exact kernel at once: no coarse pass at all; a BIG query row (no fp16 copy: fix_scale); fewer than two ordinary train
                 // rows (the second candidate is a padding / BIG row, whose accumulator says nothing about its distance)
-                if (a.all_to_fallback || !(nq2 < S.thr2) /* also a NaN norm: the exact kernel restates the oracle's arithmetic for it */ || !(__uint_as_float(c.y & ~a.idx_mask) < 1.0e29f)) fb = true;
+                if (a.all_to_fallback || !(nq2 < S.thr2) /* also a NaN norm: the exact kernel restates the oracle's arithmetic for it */ || key_is_pad(S, c.y, a.idx_mask)) fb = true;
                 else {
-                    const double eps = coarse_eps(S, nq2);
+                    const double eps = coarse_eps_row(S, qi, q, nq2);
                     // the train image's BIG rows never were candidates; every one of them is at least this far from the query
                     const double lb_big = big_lower_bound(ti.bigmin, nq2);
                     const double slack = S.rel_slack * (nq2 + S.n_max * S.n_max);
                     // every row has acc >= trunc(best); both candidates have acc < trunc(second)+quantum
-                    const double lo = (double)__uint_as_float(c.x & ~a.idx_mask);
-                    const double hi = (double)__uint_as_float((c.y & ~a.idx_mask) + a.idx_mask + 1u);
+                    const double lo = key_lo(S, c.x, a.idx_mask);
+                    const double hi = key_hi(S, c.y, a.idx_mask);
                     double lb0 = fmin(acc_to_d2(S, nq2, lo - eps) - slack, lb_big);
                     const double ub1 = acc_to_d2(S, nq2, hi + eps) + slack;
                     if (lb0 < 0.0) lb0 = 0.0;
@@ -824,13 +975,13 @@ __global__ __launch_bounds__(RCN_FT) void k_filter(RerankArgs a)
                     // so the test holding at (ub0, lbnc) holds for the exact pair; ub0 < lbnc makes
                     // the candidate the unique nearest neighbour.  No distance needs recomputing.
                     if (surv && ti.K > 2) {
-                        const double hi0 = (double)__uint_as_float((c.x & ~a.idx_mask) + a.idx_mask + 1u);
-                        const double lo1 = (double)__uint_as_float(c.y & ~a.idx_mask);
+                        const double hi0 = key_hi(S, c.x, a.idx_mask);
+                        const double lo1 = key_lo(S, c.y, a.idx_mask);
                         const double ub0 = acc_to_d2(S, nq2, hi0 + eps) + slack;
                         double lbnc = fmin(acc_to_d2(S, nq2, lo1 - eps) - slack, lb_big);
                         if (lbnc < 0.0) lbnc = 0.0;
                         if (ub0 >= 0.0 && ub0 < lbnc && ratio_pass(ub0, lbnc, a.ratio)) {
-                            res = (int32_t)(c.x & a.idx_mask);
+                            res = (int32_t)key_idx(S, c.x, a.idx_mask);
                             surv = false;
                         }
                     }
@@ -897,7 +1048,7 @@ __global__ __launch_bounds__(64) void k_rerank_lds(RerankArgs a)
         const ImgDev qi = a.imgs[a.pairs[2 * pair]];
         const ImgDev ti = a.imgs[a.pairs[2 * pair + 1]];
         const uint2 c = a.cand[(size_t)pair * a.kq_stride + q];
-        int ia = (int)(c.x & a.idx_mask), ib = (int)(c.y & a.idx_mask);
+        int ia = key_idx(S, c.x, a.idx_mask), ib = key_idx(S, c.y, a.idx_mask);
         if (ib >= ti.K) ib = ia;      // (a padding row as second candidate: k_filter keeps such rows off this list; never an address)
         __syncthreads();  // previous group's reads of rowptr/tile are done
         rowptr[lane] = qi.f32 + (size_t)q * D;
@@ -943,8 +1094,8 @@ __global__ __launch_bounds__(64) void k_rerank_lds(RerankArgs a)
             int res = -2;
             if (ti.K > 2 && ib != ia) {
                 const double nq2 = qi.nrm2[q];
-                const double lbacc = (double)__uint_as_float(c.y & ~a.idx_mask);
-                const double lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps(S, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
+                const double lbacc = key_lo(S, c.y, a.idx_mask);
+                const double lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps_row(S, qi, q, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
                 res = certify(ea, ia, eb, lbnc, a.ratio);
             }
             if (res >= 0) a.out[(size_t)pair * a.out_stride + q] = res;
@@ -965,7 +1116,7 @@ __global__ void k_rerank_generic(RerankArgs a)
         const ImgDev qi = a.imgs[a.pairs[2 * pair]];
         const ImgDev ti = a.imgs[a.pairs[2 * pair + 1]];
         const uint2 c = a.cand[(size_t)pair * a.kq_stride + q];
-        int ia = (int)(c.x & a.idx_mask), ib = (int)(c.y & a.idx_mask);
+        int ia = key_idx(S, c.x, a.idx_mask), ib = key_idx(S, c.y, a.idx_mask);
         const float *qrow = qi.f32 + (size_t)q * a.D;
         double ea = exact_d2<false>(qrow, ti.f32 + (size_t)ia * a.D, a.D);
         double eb = exact_d2<false>(qrow, ti.f32 + (size_t)ib * a.D, a.D);
@@ -973,8 +1124,8 @@ __global__ void k_rerank_generic(RerankArgs a)
         double lbnc = INFINITY;
         if (ti.K > 2) {
             const double nq2 = qi.nrm2[q];
-            const double lbacc = (double)__uint_as_float(c.y & ~a.idx_mask);
-            lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps(S, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
+            const double lbacc = key_lo(S, c.y, a.idx_mask);
+            lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps_row(S, qi, q, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
         }
         int res = certify(ea, ia, eb, lbnc, a.ratio);
         if (res == -2) {
@@ -1126,7 +1277,7 @@ __global__ __launch_bounds__(64 * EX_WAVES) void k_exact_rows_lds(const ImgDev *
 // An uncertified row needs its EXACT two nearest neighbours.  Round 3 sent it straight to K2b: one workgroup per row, all
 // K2 train rows through the fp64 chain -- and, what costs more, all K2 x D x 4 bytes of the train image read for ONE query
 // (cfg 3: 114 476 rows x 4 MB = 480 GB per step through L2 / Infinity Cache: 68.8 ms).  Here the rows are binned by TRAIN
-// image, so that sixteen of them share one sweep over that image, and the sweep runs in fp32 (sub + fma per element, eight
+// image, so that RCN_MIDQ of them share one sweep over that image, and the sweep runs in fp32 (sub + fma per element, eight
 // times the fp64 chain's rate).  fp32 values cannot decide anything, but they can EXCLUDE: with
 //     g = (D + 8) 2^-23   (relative error of a D-term fp32 sum of squares of fp32 differences, with room)
 // every row whose exact distance is <= U has fp32 value <= U (1 + g) + tiny, so the rows with value <= thr = U (1 + g) + tiny
@@ -1139,7 +1290,8 @@ __global__ __launch_bounds__(64 * EX_WAVES) void k_exact_rows_lds(const ImgDev *
 // (value, index)-ordered top-2 of THOSE is the top-2 of all rows: same bits as K2b.  A list that overflows, and whatever
 // exceeds the tier's row budget, still goes to K2b.
 #define RCN_MIDCAP 32          // candidates kept per row
-#define RCN_MIDQ 16            // query rows per sweep of a train image
+#define RCN_MIDQ 32            // query rows per sweep of a train image (16 until the int8 coarse pass, which sends 50 times the rows here -- 1600 per train
+                               // image and cfg-3 step -- so that sweeps are full either way: exact stages of a 32 640-pair launch 21.5 -> 19.2 ms)
 #define RCN_MIDROWS (1 << 21)  // rows per pipeline chunk the tier takes (the rest: K2b)
 struct MidArgs {
     const ImgDev *imgs;
@@ -1228,10 +1380,10 @@ __device__ __forceinline__ float mid_threshold(const MidArgs &a, const ScaleDev 
         const ImgDev qi = a.imgs[a.pairs[2 * pair]];
         const double nq2 = qi.nrm2[q];
         const uint2 c = a.cand[(size_t)pair * a.kq_stride + q];
-        if (nq2 < S.thr2 && __uint_as_float(c.y & ~a.idx_mask) < 1.0e29f) {
+        if (nq2 < S.thr2 && !key_is_pad(S, c.y, a.idx_mask)) {
             // two ordinary rows (the coarse candidates) are within ub1 of the query: so is the exact second neighbour
-            const double hi = (double)__uint_as_float((c.y & ~a.idx_mask) + a.idx_mask + 1u);
-            const double ub1 = acc_to_d2(S, nq2, hi + coarse_eps(S, nq2)) + S.rel_slack * (nq2 + S.n_max * S.n_max);
+            const double hi = key_hi(S, c.y, a.idx_mask);
+            const double ub1 = acc_to_d2(S, nq2, hi + coarse_eps_row(S, qi, q, nq2)) + S.rel_slack * (nq2 + S.n_max * S.n_max);
             if (ub1 >= 0.0) {
                 const double tv = (ub1 * (1.0 + g) + 1.0e-30) * (1.0 + 1.0e-6);
                 thr = tv < 3.0e38 ? (float)tv : INFINITY;      // a threshold that does not fit fp32 decides nothing: two sweeps
@@ -1612,7 +1764,8 @@ static void free_image(ImgHost &im)
     if (im.hn) (void)hipFree(im.hn);
     if (im.nrm2) (void)hipFree(im.nrm2);
     if (im.bigmin) (void)hipFree(im.bigmin);
-    im.f32 = nullptr; im.f16 = nullptr; im.hn = nullptr; im.nrm2 = nullptr; im.bigmin = nullptr;
+    if (im.i8n) (void)hipFree(im.i8n);
+    im.f32 = nullptr; im.f16 = nullptr; im.hn = nullptr; im.nrm2 = nullptr; im.bigmin = nullptr; im.i8n = nullptr;
 }
 
 static void free_slab(Slab &sl)
@@ -1621,6 +1774,7 @@ static void free_slab(Slab &sl)
     if (sl.hn) (void)hipFree(sl.hn);
     if (sl.nrm2) (void)hipFree(sl.nrm2);
     if (sl.bigmin) (void)hipFree(sl.bigmin);
+    if (sl.i8n) (void)hipFree(sl.i8n);
     if (sl.own_f32) (void)hipFree(sl.own_f32);
     if (sl.own_Ks) (void)hipFree(sl.own_Ks);
     sl = Slab();
@@ -1718,6 +1872,7 @@ static int upload_common(rcn_ctx *ctx, int32_t img_id, const float *src, bool sr
         RCN_HIP(hipMalloc(&im.hn, (size_t)Kp * sizeof(float)));
         RCN_HIP(hipMalloc(&im.nrm2, (size_t)Kp * sizeof(double)));
         RCN_HIP(hipMalloc(&im.bigmin, sizeof(unsigned long long)));
+        if (DPa == 256) RCN_HIP(hipMalloc(&im.i8n, (size_t)Kp * sizeof(float2)));      // int8 path: a candidate at this D only
     }
     if (K > 0) {
         RCN_HIP(hipMemcpyAsync(im.f32, src, (size_t)K * D * sizeof(float),
@@ -1786,6 +1941,7 @@ int rcn_int_slab_attach(rcn_ctx *ctx, int32_t first_id, int32_t n_images, int32_
         RCN_HIP(hipMalloc(&sl.hn, (size_t)n_slots * Kp * sizeof(float)));
         RCN_HIP(hipMalloc(&sl.nrm2, (size_t)n_slots * K * sizeof(double)));
         RCN_HIP(hipMalloc(&sl.bigmin, (size_t)n_slots * sizeof(unsigned long long)));
+        if (DPa == 256) RCN_HIP(hipMalloc(&sl.i8n, (size_t)n_slots * Kp * sizeof(float2)));
         for (size_t i = 0; i < ctx->slabs.size() && si < 0; ++i)
             if (!ctx->slabs[i].live) { ctx->slabs[i] = sl; si = (int)i; }      // reuse a retired position
         if (si < 0) { ctx->slabs.push_back(sl); si = (int)ctx->slabs.size() - 1; }
@@ -1810,6 +1966,7 @@ int rcn_int_slab_attach(rcn_ctx *ctx, int32_t first_id, int32_t n_images, int32_
         im.hn = sl.hn + (size_t)i * Kp;
         im.nrm2 = sl.nrm2 + (size_t)i * K;
         im.bigmin = sl.bigmin + i;
+        im.i8n = sl.i8n ? sl.i8n + (size_t)i * Kp : nullptr;
         auto it = ctx->images.find(first_id + i);
         if (it != ctx->images.end()) im.slot = it->second.slot;
         ctx->images[first_id + i] = im;
@@ -1911,6 +2068,13 @@ template <int DP> static void launch_prepare_batch(rcn_ctx *ctx, const Slab &sl)
     k_prepare_batch<DP><<<(unsigned)((nthr + 255) / 256), 256, 0, ctx->stream>>>(
         sl.f32 + f * sl.K * sl.D, sl.nrm2 + f * sl.K, sl.conv_n, sl.K, sl.Kp, sl.D, ctx->scale_dev.as<ScaleDev>(),
         sl.f16 + f * sl.Kp * DP, sl.hn + f * sl.Kp, sl.Ks_dev ? sl.Ks_dev + f : nullptr, sl.bigmin + f);
+    if (DP == 256 && ctx->i8_allowed) {      // the int8 conversion of the same slots: whichever fix_scale chose does the work, the other returns at once
+        const long nthr8 = (long)sl.conv_n * sl.Kp * 16;
+        k_prepare_i8<<<(unsigned)((nthr8 + 255) / 256), 256, 0, ctx->stream>>>(
+            sl.f32 + f * sl.K * sl.D, sl.nrm2 + f * sl.K, sl.conv_n, sl.K, sl.Kp, sl.D, ctx->scale_dev.as<ScaleDev>(),
+            reinterpret_cast<signed char *>(sl.f16 + f * sl.Kp * DP), (long)sl.Kp * DP * (long)sizeof(_Float16), reinterpret_cast<int *>(sl.hn + f * sl.Kp), sl.i8n + f * sl.Kp,
+            sl.Ks_dev ? sl.Ks_dev + f : nullptr, sl.bigmin + f, ctx->counters.as<unsigned>() + RCN_I8_WORD);
+    }
 }
 
 template <int DP> static void launch_prepare(rcn_ctx *ctx, const ImgHost &im)
@@ -1919,6 +2083,10 @@ template <int DP> static void launch_prepare(rcn_ctx *ctx, const ImgHost &im)
     k_fill_inf<<<1, 64, 0, ctx->stream>>>(im.bigmin, 1);
     k_prepare<DP><<<(n + 255) / 256, 256, 0, ctx->stream>>>(im.f32, im.nrm2, im.K, im.Kp, ctx->D, ctx->scale_dev.as<ScaleDev>(),
                                                             im.f16, im.hn, im.bigmin);
+    if (DP == 256 && ctx->i8_allowed)
+        k_prepare_i8<<<(im.Kp * 16 + 255) / 256, 256, 0, ctx->stream>>>(im.f32, im.nrm2, 1, im.K, im.Kp, ctx->D, ctx->scale_dev.as<ScaleDev>(),
+                                                                       reinterpret_cast<signed char *>(im.f16), 0L, reinterpret_cast<int *>(im.hn), im.i8n,
+                                                                       nullptr, im.bigmin, ctx->counters.as<unsigned>() + RCN_I8_WORD);
 }
 
 // Host copies of the scale constants after a device-side fix (k_fix_scale): one small read behind the stream.
@@ -1931,7 +2099,16 @@ int rcn_int_resolve_scale(rcn_ctx *ctx)
     ctx->bias = ctx->scale_host.bias;
     ctx->max_norm = ctx->scale_host.n_max;
     ctx->thr2 = ctx->scale_host.thr2;
+    ctx->coarse_i8_host = ctx->scale_host.coarse_i8;
     ctx->scale_on_device = false;
+    return RCN_OK;
+}
+
+int rcn_int_i8_commit(rcn_ctx *ctx)
+{
+    if (!ctx->i8_allowed) return RCN_OK;
+    k_i8_commit<<<1, 64, 0, ctx->stream>>>(ctx->counters.as<unsigned>() + RCN_I8_WORD, ctx->scale_dev.as<ScaleDev>());
+    RCN_HIP(hipGetLastError());
     return RCN_OK;
 }
 
@@ -1949,9 +2126,15 @@ int rcn_int_prepare_all(rcn_ctx *ctx)
     bool on_device = ctx->want_dev_scale;
     if (on_device)
         for (const auto &kv : ctx->images) on_device = on_device && kv.second.dirty;
-    bool moved = false;
+    // the int8 coarse pass: what the host knows of its preconditions; a change of that reconverts everything like a moved scale
+    bool allow_i8 = ctx->DP == 256 && !ctx->coarse_i8_off && !ctx->coarse_w4 && ctx->coarse_shape < 0 && !ctx->force_exact;
+    for (const auto &kv : ctx->images) allow_i8 = allow_i8 && kv.second.Kp <= (1 << RCN_I8_IDX_BITS) && kv.second.i8n;
+    bool moved = allow_i8 != ctx->i8_allowed;
+    ctx->i8_allowed = allow_i8;
+    unsigned *i8_max = ctx->counters.as<unsigned>() + RCN_I8_WORD;
     if (on_device) {
-        k_fix_scale<<<1, 64, 0, ctx->stream>>>(ctx->counters.as<unsigned>(), DPa, ctx->scale_dev.as<ScaleDev>());
+        RCN_HIP(hipMemsetAsync(i8_max, 0, 2 * sizeof(unsigned), ctx->stream));      // every image is converted below
+        k_fix_scale<<<1, 64, 0, ctx->stream>>>(ctx->counters.as<unsigned>(), DPa, allow_i8 ? 1 : 0, ctx->scale_dev.as<ScaleDev>());
         RCN_HIP(hipGetLastError());
         ctx->scale_on_device = true;
     } else {
@@ -1980,9 +2163,11 @@ int rcn_int_prepare_all(rcn_ctx *ctx)
         double maxn2;
         memcpy(&maxabs, &hc[0], 4);
         memcpy(&maxn2, &hc[2], 8);
-        fix_scale(maxabs, maxn2, hc.data() + RCN_HIST_WORD, DPa, &ctx->scale_host);
+        fix_scale(maxabs, maxn2, hc.data() + RCN_HIST_WORD, DPa, allow_i8 ? 1 : 0, &ctx->scale_host);
         const double s = ctx->scale_host.s, bias = ctx->scale_host.bias;
-        moved = s != ctx->scale || bias != ctx->bias || ctx->scale_host.thr2 != ctx->thr2;
+        moved = moved || s != ctx->scale || bias != ctx->bias || ctx->scale_host.thr2 != ctx->thr2 || ctx->scale_host.coarse_i8 != ctx->coarse_i8_host;
+        ctx->coarse_i8_host = ctx->scale_host.coarse_i8;
+        if (moved) RCN_HIP(hipMemsetAsync(i8_max, 0, 2 * sizeof(unsigned), ctx->stream));   // maxima of the rows converted at THIS scale
         ctx->thr2 = ctx->scale_host.thr2;
         ctx->scale = s;
         ctx->max_norm = ctx->scale_host.n_max;
@@ -2009,7 +2194,7 @@ int rcn_int_prepare_all(rcn_ctx *ctx)
             RCN_HIP(hipGetLastError());
         }
         im.dirty = false;
-        table.push_back(ImgDev{im.f32, im.f16, im.hn, im.nrm2, im.bigmin, im.K, im.Kp});
+        table.push_back(ImgDev{im.f32, im.f16, im.hn, im.nrm2, im.bigmin, im.K, im.Kp, im.i8n});
     }
     if (ctx->DP)
         for (size_t si = 0; si < ctx->slabs.size(); ++si) {
@@ -2023,6 +2208,7 @@ int rcn_int_prepare_all(rcn_ctx *ctx)
             }
             RCN_HIP(hipGetLastError());
         }
+    { int rci = rcn_int_i8_commit(ctx); if (rci) return rci; }      // (the host path's upload of the scale record cleared rho / tau: always behind it)
     // the image table: uploaded only when it differs from what the device already holds (a per-step exchange into the
     // same landing buffer leaves it unchanged); the staging vector lives in the ctx, so nothing waits for the copy
     const bool same = table.size() == ctx->table_host.size() && ctx->img_table.p &&
@@ -2055,6 +2241,16 @@ template <int DP, int ABL = 0, int SH = 0> static hipError_t launch_coarse(rcn_c
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     k_coarse_top2<DP, ABL, SH><<<blocks, 512, lds, ctx->stream>>>(ca);
+    return hipGetLastError();
+}
+
+template <int ABL, int SH> static hipError_t launch_coarse_i8(rcn_ctx *ctx, const CoarseArgs &ca, int blocks)
+{
+    const size_t lds = (size_t)RCN_NBUF * (RCN_I8_BT * 256 + 8 * RCN_I8_BT * 4) + RCN_TBL_BYTES;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_coarse_top2_i8<ABL, SH>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    k_coarse_top2_i8<ABL, SH><<<blocks, 512, lds, ctx->stream>>>(ca);
     return hipGetLastError();
 }
 
@@ -2281,6 +2477,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
             const int64_t items = (int64_t)ng_c * tiles;
             ca.items_per_xcd = (int)((items + 7) / 8);
             ca.idx_mask = idx_mask;
+            ca.sc = ctx->scale_dev.as<ScaleDev>();
             const int blocks = ca.items_per_xcd * 8;
             hipError_t e;
             if (ctx->coarse_w4 && ctx->DP >= 64) {
@@ -2333,6 +2530,19 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
                 }
             }
             RCN_HIP(e);
+            // the int8 form of K1 (D padded to 256, at most 4096 padded rows per image): fix_scale chose between the two on the device, the
+            // host launches both and the one whose flag does not match returns at once.
+            // MFMA shape: v_mfma_i32_16x16x64_i8 (A/B on one box, EXPERIMENTS.md section 4: 108.0 ms per 32 640-pair launch against 117.8 ms on
+            // v_mfma_i32_32x32x32_i8 and 198.8 ms on the fp16 kernel)
+            if (ctx->i8_allowed) {
+#ifdef RCN_DIAG
+                if (ctx->coarse_i8_shape == 0) e = launch_coarse_i8<0, 0>(ctx, ca, blocks);
+                else if (ctx->ablate == 1) e = launch_coarse_i8<1, 1>(ctx, ca, blocks);      // timing only: no top-2 fold
+                else
+#endif
+                e = launch_coarse_i8<0, 1>(ctx, ca, blocks);
+                RCN_HIP(e);
+            }
         }
         if (tm) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][1], st));
         ra.cand = cand_c;
@@ -2444,6 +2654,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
     ctx->last_stats.rows_total = rows;
     ctx->last_stats.pair_distances = pd;
     ctx->last_stats.used_mfma_path = mfma ? 1 : 0;
+    ctx->last_stats.coarse_dtype = mfma ? -1 : 0;      // which of the two: from the scale record, lazily (rcn_match_last_stats)
     ctx->last_stats.rows_exact_fallback = -1;
     ctx->last_stats.err_bound_d2 = -1.0;      // from the scale constants, lazily (rcn_match_last_stats)
     return RCN_OK;
@@ -2638,10 +2849,21 @@ int rcn_match_last_stats(const rcn_ctx *cctx, rcn_match_stats *out)
         ctx->last_stats.rows_reranked = n[1];
         ctx->last_stats.rows_brute_force = n[2];
     }
+    if (ctx->last_stats.coarse_dtype < 0) {
+        { int rcs = rcn_int_resolve_scale(ctx); if (rcs) return rcs; }
+        ctx->last_stats.coarse_dtype = ctx->i8_allowed && ctx->coarse_i8_host ? 2 : 1;
+    }
+    if (ctx->last_stats.err_bound_d2 < 0.0 && ctx->scale_dev.p && ctx->last_stats.coarse_dtype == 2) {
+        // int8: E(q) at |qq| = tau, |rq| = rho (the largest norms any row has), as a squared distance
+        ScaleDev m;
+        RCN_HIP(hipMemcpyAsync(&m, ctx->scale_dev.p, sizeof(ScaleDev), hipMemcpyDeviceToHost, ctx->stream));
+        RCN_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->last_stats.err_bound_d2 = 2.0 * (2.0 * m.tau * m.rho + m.rho * m.rho + 0.5) / m.s2;
+    }
     if (ctx->last_stats.err_bound_d2 < 0.0 && ctx->scale_dev.p) {
         { int rcs = rcn_int_resolve_scale(ctx); if (rcs) return rcs; }
         ScaleDev m;
-        fix_scale(1.f, 1.0, nullptr, ctx->DP ? ctx->DP : 32, &m);        // c_acc only depends on DP
+        fix_scale(1.f, 1.0, nullptr, ctx->DP ? ctx->DP : 32, 0, &m);        // c_acc only depends on DP
         const double s2 = ctx->scale * ctx->scale, nq = ctx->max_norm, u = std::ldexp(1.0, -11);
         const double hn_max = 0.5 * s2 * nq * nq + ctx->bias;
         const double eps = (2 * u + u * u) * s2 * nq * nq + std::ldexp(1.0, -14) * std::sqrt((double)(ctx->DP ? ctx->DP : 32)) * ctx->scale * 2 * nq +
@@ -2697,6 +2919,41 @@ int rcn_diag_coarse_table(rcn_ctx *ctx, uint32_t *cand_host, int64_t capacity_wo
     RCN_HIP(hipSetDevice(ctx->device));
     RCN_HIP(hipMemcpyAsync(cand_host, ctx->cand.p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     RCN_HIP(hipStreamSynchronize(ctx->stream));
+    return RCN_OK;
+}
+#endif
+
+#ifdef RCN_DIAG
+// Diagnostic build only: the int8 coarse pass as the device left it.  model[8] = {coarse_i8 (0 / 1), s, BIAS, rho, tau, Nmax, i8_allowed, 0};
+// for image img_id (any pointer may be NULL): q_host K x 256 quantised elements in natural order, hn_host K integer half-norms,
+// norms_host K x 2 stored (|xq|, |s x - xq|).
+int rcn_diag_i8(rcn_ctx *ctx, double *model, int32_t img_id, int8_t *q_host, int32_t *hn_host, float *norms_host)
+{
+    if (!ctx || !model) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->scale_dev.p || !ctx->prepared) { ctx->set_error("rcn_diag_i8: nothing prepared"); return RCN_ERR_ARG; }
+    RCN_HIP(hipSetDevice(ctx->device));
+    ScaleDev m;
+    RCN_HIP(hipMemcpyAsync(&m, ctx->scale_dev.p, sizeof(ScaleDev), hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipStreamSynchronize(ctx->stream));
+    model[0] = m.coarse_i8; model[1] = m.s; model[2] = m.bias; model[3] = m.rho; model[4] = m.tau; model[5] = m.n_max;
+    model[6] = ctx->i8_allowed ? 1.0 : 0.0; model[7] = 0.0;
+    if (!q_host && !hn_host && !norms_host) return RCN_OK;
+    auto it = ctx->images.find(img_id);
+    if (it == ctx->images.end()) { ctx->set_error("rcn_diag_i8: image id not resident"); return RCN_ERR_NOT_FOUND; }
+    if (!m.coarse_i8 || !it->second.i8n) { ctx->set_error("rcn_diag_i8: the resident set holds no int8 copies"); return RCN_ERR_UNSUPPORTED; }
+    const ImgHost &im = it->second;
+    if (im.K <= 0) return RCN_OK;
+    std::vector<int8_t> raw((size_t)im.K * 256);
+    std::vector<float> nn((size_t)im.K * 2);
+    RCN_HIP(hipMemcpyAsync(raw.data(), im.f16, raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (hn_host) RCN_HIP(hipMemcpyAsync(hn_host, im.hn, (size_t)im.K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipMemcpyAsync(nn.data(), im.i8n, nn.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipStreamSynchronize(ctx->stream));
+    if (q_host)
+        for (int r = 0; r < im.K; ++r)
+            for (int c = 0; c < 16; ++c) memcpy(q_host + (size_t)r * 256 + 16 * c, raw.data() + (size_t)r * 256 + ((c ^ (r & 15)) << 4), 16);
+    if (norms_host) memcpy(norms_host, nn.data(), nn.size() * sizeof(float));
     return RCN_OK;
 }
 #endif

@@ -42,11 +42,13 @@ struct DevBuf {
 // Per-image device record (mirrored in a device table for the kernels).
 struct ImgDev {
     const float *f32;      // [K][D]      original rows (exact re-rank reads these)
-    const _Float16 *f16;   // [Kp][DP]    scaled by the global power of two, 16-B chunks XOR-swizzled
-    const float *hn;       // [Kp]        0.5*s^2*|t|^2 + BIAS ; padded rows = huge
+    const _Float16 *f16;   // [Kp][DP]    scaled by the global power of two, 16-B chunks XOR-swizzled; int8 path (ScaleDev::coarse_i8): int8 [Kp][256] in the
+                           //             same allocation, rint(s x), same swizzle idea (256-byte rows)
+    const float *hn;       // [Kp]        0.5*s^2*|t|^2 + BIAS ; padded rows = huge; int8 path: int32 rint(s^2 |t|^2 / 2) + BIAS, padded rows 2^20 - 1
     const double *nrm2;    // [K]         |x|^2 in fp64
     const unsigned long long *bigmin;   // bits of the smallest |x|^2 among this image's BIG rows (+infinity: it has none)
     int32_t K, Kp;
+    const float2 *i8n;     // [Kp]        int8 path only: (|xq|, |s x - xq|) of the row, both rounded UP (k_prepare_i8)
 };
 
 struct ImgHost {
@@ -55,6 +57,7 @@ struct ImgHost {
     float *hn = nullptr;
     double *nrm2 = nullptr;
     unsigned long long *bigmin = nullptr;
+    float2 *i8n = nullptr;
     int32_t K = 0, Kp = 0;
     int32_t slot = -1;  // row in the device image table
     int32_t slab = -1;  // >= 0: buffers are views into ctx->slabs[slab] (batch upload)
@@ -75,11 +78,14 @@ struct Slab {
     float *hn = nullptr;
     double *nrm2 = nullptr;
     unsigned long long *bigmin = nullptr;   // [n] one word per slot
+    float2 *i8n = nullptr;                  // [n][Kp] quantised / residual norms of the int8 path
     bool live = false;
 };
 
-// ctx->counters (words): [0] max |x| bits, [2..3] max |x|^2 bits, [8..15] per-chunk list counts, then the histogram of rows per
-// octave of |x|^2 (match.hip, k_rowstats / fix_scale)
+// ctx->counters (words): [0] max |x| bits, [2..3] max |x|^2 bits, [8..15] per-chunk list counts, [16] / [17] int8 path: fp32 bits of the largest
+// residual norm / quantised norm over the rows converted at the scale in force, then the histogram of rows per octave of |x|^2
+// (match.hip, k_rowstats / fix_scale)
+#define RCN_I8_WORD 16
 #define RCN_HIST_BINS 512
 #define RCN_HIST_WORD 64
 #define RCN_COUNTER_BYTES ((RCN_HIST_WORD + RCN_HIST_BINS) * 4)
@@ -101,6 +107,12 @@ struct ScaleDev {
     double thr2;        // rows with |x|^2 >= thr2 are BIG rows (fix_scale, match.hip); +infinity: none
     float  sf;          // (float)s
     float  pad;
+    // int8 coarse pass (fix_scale chooses it on the device).  When coarse_i8 is set, s is 127 / max |x| or
+    // less (not a power of two), bias an integer, and the fp16 constants above (c_in, c_sub, c_acc) are unused.
+    double rho;         // max |s t - tq| over the rows converted at this scale, rounded up (k_i8_commit)
+    double tau;         // max |tq| over the same rows, rounded up
+    int32_t coarse_i8;  // 1: the resident images hold int8 copies and integer half-norms
+    int32_t pad2;
 };
 
 // fused table filter (fmat.hip): per-pair keypoint coordinate lists
@@ -144,6 +156,9 @@ struct rcn_ctx {
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)
+    bool i8_allowed = false;        // what the host knows of the int8 path's preconditions held at the last prepare (D padded to 256, every image at
+                                    // most 4096 padded rows, no diagnostic switch against it); the data-dependent part is fix_scale's
+    int32_t coarse_i8_host = 0;     // ScaleDev::coarse_i8 of the scale in force (stale while scale_on_device)
     std::vector<ImgDev> table_host; // image table as last uploaded (unchanged tables are not uploaded again)
     DevBuf img_table, pairs_dev, groups_dev, cand, owner, fb_list, sv_list, counters, out_tmp, cnt_tmp;
     hipEvent_t f32_ready = nullptr;   // shard.hip: set while an all-gather of fp32 rows may be in flight on a side stream
@@ -174,6 +189,8 @@ struct rcn_ctx {
     // library they are compile-time constants and the alternative code is dead.
 #ifdef RCN_DIAG
     bool coarse_w4 = false;    // RCN_COARSE_W4=1: the one-wave-per-SIMD form of K1 (k_coarse_w4, coarse_w4.h) instead of k_coarse_top2
+    bool coarse_i8_off = false;   // RCN_COARSE_I8=0: never the int8 coarse pass (tools/mfma_error_model.py measures the fp16 kernel)
+    int coarse_i8_shape = -1;  // RCN_COARSE_I8_S16=0/1: force the int8 kernel's MFMA shape (0: 32x32x32, 1: 16x16x64); -1: the shipping choice (16x16x64)
     int coarse_shape = -1;     // RCN_COARSE_S16=0/1: force k_coarse_top2's MFMA shape (0: 32x32x16, 1: 16x16x32) at every D; -1: the shipping choice
     int ablate = 0;            // RCN_COARSE_ABL
     bool force_exact = false;  // RCN_FORCE_EXACT=1: skip the MFMA coarse pass
@@ -183,6 +200,8 @@ struct rcn_ctx {
     bool ba_pair_small = true; // RCN_PAIR_SMALL=0: the pair lists of the smallest graphs by the six general launches too
 #else
     static constexpr bool coarse_w4 = false;
+    static constexpr bool coarse_i8_off = false;
+    static constexpr int coarse_i8_shape = -1;
     static constexpr int coarse_shape = -1;
     static constexpr int ablate = 0;
     static constexpr bool force_exact = false, no_item_order = false, ba_atomics = false, ba_trsv_fwd = false, ba_pair_small = true;
@@ -298,6 +317,8 @@ int rcn_int_slab_attach(rcn_ctx *ctx, int32_t first_id, int32_t n_images, int32_
                         const int32_t *Ks_host, const int32_t *Ks_dev);
 int rcn_int_slab_rowstats(rcn_ctx *ctx, int slab, int32_t first, int32_t n);
 int rcn_int_prepare_all(rcn_ctx *ctx);
+int rcn_int_i8_commit(rcn_ctx *ctx);         // int8 path: the residual / quantised-norm maxima of ctx->counters into the scale record (behind the conversions,
+                                             // and behind their reduction over the ranks of a sharded grid)
 int rcn_int_resolve_scale(rcn_ctx *ctx);     // host copies of scale / bias / max_norm are current afterwards (may synchronise)
 int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                        int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);

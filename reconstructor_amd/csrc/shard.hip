@@ -587,7 +587,17 @@ int rcn_shard_exchange(rcn_shard *sh, const float *local_desc_dev, const int32_t
     softn(ncclAllGather(hn + sh->rank * blkhn, hn, blkhn, ncclChar, sh->comm, st), "ncclAllGather(half-norms)");
     softn(ncclAllGather(n2 + sh->rank * blkn2, n2, blkn2, ncclChar, sh->comm, st), "ncclAllGather(norms)");
     softn(ncclAllGather(sl.bigmin + (size_t)sh->rank * per, sl.bigmin, (size_t)per, ncclUint64, sh->comm, st), "ncclAllGather(bigmin)");     // smallest BIG-row norm per image
+    // int8 coarse pass (fix_scale chose on the device: the host does not know, and does not wait to learn it): an image's int8 copy lies in the
+    // first half of its fp16 slot, so the gather above carries whichever copy is active; the per-row quantised / residual norms ride beside it,
+    // and the two maxima the certificates use are reduced over the ranks and committed to the scale record behind that (identical on every rank)
+    if (ctx->i8_allowed && sl.i8n) {
+        const size_t blkn8 = (size_t)per * sl.Kp * sizeof(float2);
+        char *n8 = reinterpret_cast<char *>(sl.i8n);
+        softn(ncclAllGather(n8 + sh->rank * blkn8, n8, blkn8, ncclChar, sh->comm, st), "ncclAllGather(int8 row norms)");
+        if (world > 1) softn(ncclAllReduce(cw + RCN_I8_WORD, cw + RCN_I8_WORD, 2, ncclUint32, ncclMax, sh->comm, st), "ncclAllReduce(int8 maxima)");
+    }
     softn(ncclGroupEnd(), "ncclGroupEnd");
+    if (world > 1 && !p2) softrc(rcn_int_i8_commit(ctx));
     // fp32 rows: on the side stream with their own communicator, behind the fp16 payload (so the two do
     // not share the links while the coarse kernel is waiting) and hence behind (a) the local block being
     // in place and (b) every reader of the previous batch -- all earlier work of the ctx stream.  The

@@ -19,6 +19,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+# this tool measures the fp16 error model on the fp16 kernel: the int8 coarse pass (which 256-d rows such as the first data set
+# would otherwise take) is switched off for the ctx created below (diagnostic build: rcn_create reads the switch)
+os.environ["RCN_COARSE_I8"] = "0"
 
 
 def data_sets():
