@@ -550,6 +550,42 @@ int rcn_landmark_attach(rcn_ctx *ctx, const double *pose34, const double *intr6,
                         const int32_t *landmark, const int32_t *feat, const int32_t *xy, double max_projection_error,
                         uint8_t *status_out, int32_t *n_attached_out);
 
+/* ---- view registration: P3P-RANSAC + refit ----------------------------------------------------
+ * SequentialReconstructor::registerImagePnP (SequentialReconstructor.cpp:559-638) for a batch of views: cv::solvePnPRansac
+ * in its P3P mode (4-entry samples from cv::RNG, closed-form 3-point solver, the fourth entry picks the solution; squared
+ * reprojection error against max_projection_error^2 in float; OpenCV's update of the iteration count) and a damped
+ * Gauss-Newton refit of the best model on its inliers.  The reference passes the default flag (EPnP on 5-entry samples):
+ * that one flag is the deliberate difference (where the whole algorithm is written down).
+ *   view v      entries off[v] .. off[v + 1] (int64, off[0] = 0): landmark index into points (n_points x 3) and integer pixel;
+ *               intr6 = fx fy cx cy k1 k2 per view
+ *   count_out   inliers of the best model; -1: no model was accepted; -2: fewer than 4 entries (or, device entry, a view
+ *               image without coordinates).  Negative: mask and poses all 0.
+ *   mask_out    1 = inlier of the best model (not recomputed after the refit)
+ *   pose34_out  rows of [R | t], the refit; ransac_pose34_out (may be NULL) the best model itself
+ *   iterations_out (may be NULL) sampling iterations executed
+ * RCN_ERR_ARG: a null pointer, decreasing offsets, a landmark outside 0 .. n_points - 1, confidence outside (0, 1), a
+ * non-positive threshold or iteration cap.  opt == NULL: the defaults. */
+typedef struct { double max_projection_error, confidence; int32_t max_iterations, refine_iterations; } rcn_pnp_options;
+void rcn_pnp_default_options(rcn_pnp_options *o);      /* 4.0, 0.99, 10000 (:596), 20 */
+int rcn_pnp_ransac(rcn_ctx *ctx, int32_t n_views, const int64_t *off, const int32_t *landmark, const int32_t *xy,
+                   int32_t n_points, const double *points, const double *intr6 /* n_views x 6 */, const rcn_pnp_options *opt,
+                   double *pose34_out /* n_views x 12 */, double *ransac_pose34_out /* may be NULL */,
+                   uint8_t *mask_out, int32_t *count_out, int32_t *iterations_out /* may be NULL */);
+/* Every pointer in DEVICE memory, asynchronous on the ctx stream after at most one small host-to-device copy (the table of
+ * resident coordinates), no host synchronisation: takes what rcn_corr_2d3d_device left (cand_off_dev, out_landmark_dev,
+ * out_feat_dev, cand_dev as view_img_dev) and reads each entry's pixel from the view image's resident coordinates
+ * (rcn_coords_upload*).  The data cannot be checked: a landmark or feature outside its array makes the entry a non-inlier
+ * that no model is built from, an image without coordinates gives count -2; nothing is read or written out of bounds.
+ * ransac_pose34_dev and iterations_dev may be NULL. */
+int rcn_pnp_ransac_device(rcn_ctx *ctx, int32_t n_views, const int64_t *off_dev, const int32_t *landmark_dev,
+                          const int32_t *feat_dev, const int32_t *view_img_dev, int32_t n_points, const double *points_dev,
+                          const double *intr6_dev, const rcn_pnp_options *opt, double *pose34_dev, double *ransac_pose34_dev,
+                          uint8_t *mask_dev, int32_t *count_dev, int32_t *iterations_dev);
+/* One view against the session's points in HBM (they are not copied): rcn_pnp_ransac on rcn_ba_session_points_device, bit
+ * for bit.  The caller then adds the camera (rcn_ba_session_add_camera). */
+int rcn_ba_session_pnp(rcn_ba_session *s, int32_t n, const int32_t *landmark, const int32_t *xy, const double *intr6,
+                       const rcn_pnp_options *opt, double *pose34_out, uint8_t *mask_out, int32_t *count_out);
+
 /* ---- epipolar filter of a pair's matches --------------------------------------------------
  * GeometricFilter::estimateFundamental (GeometricFilter.cpp:39-61) as the pair loop uses it
  * (SequentialReconstructor.cpp:237-269): cv::findFundamentalMat(pts1, pts2, mask) with OpenCV's

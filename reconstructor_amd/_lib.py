@@ -35,6 +35,7 @@ SYMBOLS = [
     "rcn_triangulate", "rcn_triangulate_device",
     "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
     "rcn_landmark_attach", "rcn_ba_session_attach",
+    "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -91,6 +92,11 @@ class TriangulationProblem(C.Structure):
                 ("reserved", C.c_int32),
                 ("poses34", C.c_void_p), ("intrinsics", C.c_void_p),
                 ("trk_off", C.c_void_p), ("obs_cam", C.c_void_p), ("obs_xy", C.c_void_p)]
+
+
+class PnpOptions(C.Structure):
+    _fields_ = [("max_projection_error", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int32),
+                ("refine_iterations", C.c_int32)]
 
 
 class BaOptions(C.Structure):
@@ -298,6 +304,14 @@ def load():
     L.rcn_landmark_attach.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
     L.rcn_ba_session_attach.restype = C.c_int
     L.rcn_ba_session_attach.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
+    L.rcn_pnp_default_options.restype = None
+    L.rcn_pnp_default_options.argtypes = [C.POINTER(PnpOptions)]
+    L.rcn_pnp_ransac.restype = C.c_int
+    L.rcn_pnp_ransac.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(PnpOptions), vp, vp, vp, vp, vp]
+    L.rcn_pnp_ransac_device.restype = C.c_int
+    L.rcn_pnp_ransac_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, C.POINTER(PnpOptions), vp, vp, vp, vp, vp]
+    L.rcn_ba_session_pnp.restype = C.c_int
+    L.rcn_ba_session_pnp.argtypes = [vp, i32, vp, vp, vp, C.POINTER(PnpOptions), vp, vp, C.POINTER(i32)]
     L.rcn_store_save.restype = C.c_int
     L.rcn_store_save.argtypes = [C.c_char_p, C.POINTER(StoreContents)]
     L.rcn_store_open.restype = C.c_int

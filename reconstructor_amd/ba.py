@@ -245,6 +245,19 @@ class BaSession:
                                                           float(max_err), st.ctypes.data, C.byref(added)))
         return st[:n], added.value
 
+    def pnp(self, landmark, xy, intr6, options=None):
+        """registerImagePnP of one view against the session's landmarks in HBM (rcn_ba_session_pnp): entries (landmark,
+        integer pixel) in list order.  Returns (pose34[12], inlier mask, count); count < 0: no pose (pnp.pnp_ransac)."""
+        lm = np.ascontiguousarray(landmark, np.int32)
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        K = np.ascontiguousarray(intr6, np.float64).reshape(6)
+        n = len(lm)
+        pose, mask, cnt = np.zeros(12), np.zeros(max(n, 1), np.uint8), C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_pnp(self.h, n, lm.ctypes.data if n else None, xy.ctypes.data if n else None,
+                                                       K.ctypes.data, C.byref(options) if options is not None else None,
+                                                       pose.ctypes.data, mask.ctypes.data, C.byref(cnt)))
+        return pose, mask[:n], cnt.value
+
     def remove_outliers(self):
         npts = self.counts()[1]
         new_idx = np.zeros(max(1, npts), np.int32)

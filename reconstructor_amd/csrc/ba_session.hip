@@ -481,4 +481,16 @@ int rcn_ba_session_attach(rcn_ba_session *s, const double *poses34_host, int32_t
     return RCN_OK;
 }
 
+// registerImagePnP (:559-638) of one view against the session's landmarks (pnp.hip): the points never leave HBM
+int rcn_ba_session_pnp(rcn_ba_session *s, int32_t n, const int32_t *landmark, const int32_t *xy, const double *intr6,
+                       const rcn_pnp_options *opt, double *pose34_out, uint8_t *mask_out, int32_t *count_out)
+{
+    if (!s || n < 0) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int64_t off[2] = {0, n};
+    return rcn_int_pnp_host(ctx, "rcn_ba_session_pnp", 1, off, landmark, xy, (int32_t)s->tracks.size(), nullptr,
+                            static_cast<const double *>(s->pts.p), intr6, opt, pose34_out, nullptr, mask_out, count_out, nullptr);
+}
+
 }  // extern "C"

@@ -1,4 +1,4 @@
-// camgeom.h -- camera geometry shared by the landmark kernels (validity.hip, triangulate.hip).  gfx950.
+// camgeom.h -- camera geometry shared by the landmark kernels (validity.hip, triangulate.hip, pnp.hip).  gfx950.
 //
 // Every operation is a separately rounded IEEE double (contraction off) in one fixed order, so that every kernel that
 // projects a landmark or measures a triangulation angle does it with the same bits.
@@ -34,6 +34,21 @@ __device__ __forceinline__ double reproj_l1(const double *P, const double *K, co
     const double u = K[0] * x + K[2], v = K[1] * y + K[3];
     *depth = l[2];
     return fabs(u - (double)ox) + fabs(v - (double)oy);
+}
+
+// The same projection with the squared L2 error (u - x)^2 + (v - y)^2: what cv::solvePnPRansac scores (pnp.hip).
+__device__ __forceinline__ double reproj_sq(const double *P, const double *K, const double *X, int32_t ox, int32_t oy)
+{
+#pragma clang fp contract(off)
+    double l[3];
+    for (int i = 0; i < 3; ++i) l[i] = ((P[4 * i] * X[0] + P[4 * i + 1] * X[1]) + P[4 * i + 2] * X[2]) + P[4 * i + 3];
+    double x = l[0] / l[2], y = l[1] / l[2];
+    const double radius = x * x + y * y;
+    const double distortion = K[4] * radius + (K[5] * radius) * radius;
+    x += distortion;
+    y += distortion;
+    const double du = (K[0] * x + K[2]) - (double)ox, dv = (K[1] * y + K[3]) - (double)oy;
+    return du * du + dv * dv;
 }
 
 // calcTriangulationAngle (:815-836): 180 acos(r1.r2 / (|r1| |r2|)) / 3.1415 for the rays from the camera centres c1, c2

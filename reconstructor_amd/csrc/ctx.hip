@@ -213,6 +213,8 @@ void rcn_destroy(rcn_ctx *ctx)
     ctx->corr.release();
     ctx->corr_ws.release(); ctx->corr_hws.release(); ctx->corr_slots.release(); ctx->att_ws.release();
     if (ctx->corr_ev) (void)hipEventDestroy(ctx->corr_ev);
+    ctx->pnp_hws.release(); ctx->pnp_slots.release();
+    if (ctx->pnp_ev) (void)hipEventDestroy(ctx->pnp_ev);
     if (ctx->ev_made) {
         for (auto &call : ctx->ev_c)
             for (auto &row : call)

@@ -220,6 +220,10 @@ struct rcn_ctx {
     std::vector<char> corr_slots_host;  // staging of corr_slots (uploaded asynchronously; corr_ev marks the copy)
     hipEvent_t corr_ev = nullptr;
     bool corr_slots_pending = false;
+    DevBuf pnp_hws, pnp_slots;          // view registration (pnp.hip): host-API staging, image id -> resident coordinates
+    std::vector<char> pnp_slots_host;   // staging of pnp_slots (uploaded asynchronously; pnp_ev marks the copy)
+    hipEvent_t pnp_ev = nullptr;
+    bool pnp_slots_pending = false;
     int64_t corr_budget = 1ll << 30;    // bytes of hit rows per batch (rcn_corr_set_workspace_bytes)
     std::vector<int> ba_graph_cam, ba_graph_pt;     // observation graph of the last plain rcn_ba_solve (host copy): an identical graph reuses the pair lists
     int ba_graph_nc = 0, ba_graph_np = 0;
@@ -296,6 +300,11 @@ int rcn_int_triangulate_check(rcn_ctx *ctx, int32_t n_cams, int32_t n_tracks, in
 size_t rcn_int_triangulate_ws_bytes(int32_t n_cams, int32_t n_tracks);
 int rcn_int_triangulate_launch(rcn_ctx *ctx, const rcn_triangulation_problem *dp, double max_err, double min_angle, void *ws,
                                double *xyz, uint8_t *status, double *compact, int32_t compact_first, int32_t *n_accepted);
+// pnp.hip: rcn_pnp_ransac with ctx->mu held; points_dev != NULL: the points are already in HBM (rcn_ba_session_pnp)
+int rcn_int_pnp_host(rcn_ctx *ctx, const char *who, int32_t n_views, const int64_t *off, const int32_t *landmark, const int32_t *xy,
+                     int32_t n_points, const double *points_host, const double *points_dev, const double *intr6,
+                     const rcn_pnp_options *opt, double *pose34_out, double *ransac_pose34_out, uint8_t *mask_out,
+                     int32_t *count_out, int32_t *iterations_out);
 // corr2d3d.hip, with ctx->mu held: step 1 of triangulateMatchedLandmarks on device arrays (rcn_ba_session_attach)
 int rcn_int_attach_check(rcn_ctx *ctx, const char *who, int32_t n_points, int32_t n, const int32_t *lm, const int32_t *feat, int32_t *n_feat);
 size_t rcn_int_attach_ws_bytes(int32_t n_feat);

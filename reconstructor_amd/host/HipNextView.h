@@ -1,6 +1,7 @@
-// HipNextView.h -- SequentialReconstructor::calc2d3dMatches, ::rankNextImages and step 1 of ::triangulateMatchedLandmarks
-// (SequentialReconstructor.cpp:643-695, :697-759, :497-512) over the reference's own containers, with the search handed to
-// rcn_corr_2d3d and the attach rules to rcn_landmark_attach (include/rcn.h).
+// HipNextView.h -- SequentialReconstructor::calc2d3dMatches, ::rankNextImages, ::registerImagePnP and step 1 of
+// ::triangulateMatchedLandmarks (SequentialReconstructor.cpp:643-695, :697-759, :559-638, :497-512) over the reference's own
+// containers, with the search handed to rcn_corr_2d3d, the pose to rcn_pnp_ransac and the attach rules to rcn_landmark_attach
+// (include/rcn.h).
 //   uploadMatches     once per reconstruction: every image's keypoint coordinates and the lists featureMatches[(i, c)] for
 //                     which i is in imgMatches[c] (calc2d3dMatches' own condition), as given (no mirror)
 //   calc2d3dMatches   the reference's signature plus the containers it reads; fills imgIdToLandmarkIds /
@@ -9,6 +10,11 @@
 //                     does not model the test).
 //   rankNextImages    the reference's own ranking code and containers (std::map keyed by score / image id) over the scores
 //                     the last calc2d3dMatches computed on the GPU: both modes and their ties exactly as the reference.
+//   registerImagePnP  SequentialReconstructor::registerImagePnP (:559-638) through rcn_pnp_ransac: returns the 4 x 4 pose and
+//                     trims both lists to the inliers, in list order.  (The reference reads the inlier INDEX list that
+//                     cv::solvePnPRansac returns as if it were a byte mask, utils.cpp:328-343; the adapter keeps the entries
+//                     whose mask is 1, which is what the code evidently means: DESIGN.md section 17.)  Throws where the
+//                     reference would go on with an empty rvec: no model, or fewer than 4 entries.
 //   attachMatchedLandmarks  step 1: rcn_landmark_attach, then push_back / landmarkId in list order.
 #pragma once
 #include <algorithm>
@@ -124,6 +130,44 @@ public:
         } else {
             throw std::runtime_error("Wrong next image ranking mode!");
         }
+    }
+
+    // :559-638.  maxProjectionError is the threshold (:596), confidence 0.99 and 10000 iterations as the reference passes them.
+    template <class Pose4 = Mat4d>
+    Pose4 registerImagePnP(int imgIdx, std::vector<int> &featureIdxs, std::vector<int> &landmarkIdxs,
+                           std::unordered_map<int, std::vector<FeaturePtr<>>> &features, const std::vector<Landmark> &landmarks,
+                           std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics)
+    {
+        if (featureIdxs.size() != landmarkIdxs.size()) throw std::runtime_error("registerImagePnP: lists of different length");
+        const size_t n = featureIdxs.size();
+        const PinholeCamera &k = imgIdx2camIntrinsics.at(imgIdx);
+        const double K[6] = {k.fX, k.fY, k.cX, k.cY, k.k1, k.k2};
+        std::vector<double> pts;
+        pts.reserve(3 * landmarks.size() + 3);
+        for (const auto &lm : landmarks) { pts.push_back(lm.x); pts.push_back(lm.y); pts.push_back(lm.z); }
+        std::vector<int32_t> xy, lid(landmarkIdxs.begin(), landmarkIdxs.end());
+        for (int f : featureIdxs) { xy.push_back(features.at(imgIdx).at(f)->featCoord.x); xy.push_back(features.at(imgIdx).at(f)->featCoord.y); }
+        rcn_pnp_options opt;
+        rcn_pnp_default_options(&opt);
+        opt.max_projection_error = maxProjectionError;
+        const int64_t off[2] = {0, (int64_t)n};
+        double P[12];
+        std::vector<uint8_t> mask(n + 1);
+        int32_t count = 0;
+        check(rcn_pnp_ransac(ctx_, 1, off, lid.data(), xy.data(), (int32_t)landmarks.size(), pts.data(), K, &opt, P, nullptr, mask.data(),
+                             &count, nullptr), "rcn_pnp_ransac");
+        if (count < 0)
+            throw std::runtime_error("registerImagePnP: no pose for image " + std::to_string(imgIdx) +
+                                     (count == -2 ? " (fewer than 4 matches)" : " (no model)"));
+        std::vector<int> keptF, keptL;
+        for (size_t e = 0; e < n; ++e)
+            if (mask[e]) { keptF.push_back(featureIdxs[e]); keptL.push_back(landmarkIdxs[e]); }
+        featureIdxs = std::move(keptF);
+        landmarkIdxs = std::move(keptL);
+        Pose4 T;
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T(r, c) = r == c ? 1.0 : 0.0;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T(r, c) = P[4 * r + c];
+        return T;
     }
 
     // step 1 of triangulateMatchedLandmarks (:497-512).  Returns the status per entry (0 attached, 1 depth,
