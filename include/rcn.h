@@ -47,9 +47,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * its arguments: a caller built against an older header must not be linked against a newer library (rcn_match_last_stats copies the whole
  * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
- * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats).
+ * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
+ * initialisation entry points and rcn_twoview_options).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 6
+#define RCN_ABI_REVISION 7
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -585,6 +586,62 @@ int rcn_pnp_ransac_device(rcn_ctx *ctx, int32_t n_views, const int64_t *off_dev,
  * for bit.  The caller then adds the camera (rcn_ba_session_add_camera). */
 int rcn_ba_session_pnp(rcn_ba_session *s, int32_t n, const int32_t *landmark, const int32_t *xy, const double *intr6,
                        const rcn_pnp_options *opt, double *pose34_out, uint8_t *mask_out, int32_t *count_out);
+
+/* ---- two-view initialisation: 5-point RANSAC + pose recovery -------------------------------------
+ * SequentialReconstructor::chooseInitialPair (SequentialReconstructor.cpp:325-375) behind its choice of the pair, for a batch
+ * of pairs: cv::findEssentialMat in its two-camera form (pixels unprojected per image, Camera.h:79-93, and renormalised by the
+ * mean of the two camera matrices; 5-entry samples from cv::RNG; Nister's five-point solver, up to ten E per sample; Sampson
+ * error in float against (threshold / mean focal)^2; OpenCV's update of the iteration count) followed by cv::recoverPose on
+ * the search's own mask (four candidates (R1, t) (R2, t) (R1, -t) (R2, -t), an entry good for a candidate iff both of its
+ * depths lie in (0, distance_threshold), the >= cascade).  DESIGN.md section 18 writes the whole algorithm down.
+ *   pair p      entries off[p] .. off[p + 1] (int64, off[0] = 0) of xy1 / xy2 (integer pixels of the matched features, in
+ *               ascending query-feature order); intr6 = fx fy cx cy k1 k2 of the first / second image of every pair
+ *   count_out   n_pairs x 2: inliers of the best E (-1: no model was accepted, -2: fewer than 5 entries; device entry: also
+ *               a pair without a resident list or without room), and entries of the cheirality mask.  Negative: every
+ *               other output 0.
+ *   E_out       n_pairs x 9 row-major, unit Frobenius norm, x2' E x1 = 0 in normalised coordinates (may be NULL)
+ *   pose34_out  rows of [R | t] of the second camera, |t| = 1; the first camera is the identity
+ *   mask_out    1 = inlier of the best E; cheir_mask_out (may be NULL) 1 = inlier in front of both cameras of the winner
+ *   iterations_out (may be NULL) sampling iterations executed
+ * RCN_ERR_ARG: a null pointer, decreasing offsets, confidence outside (0, 1), a non-positive threshold, distance or
+ * iteration cap.  opt == NULL: the defaults. */
+typedef struct { double threshold, confidence, distance_threshold; int32_t max_iterations, reserved; } rcn_twoview_options;
+void rcn_twoview_default_options(rcn_twoview_options *o);      /* 1.0, 0.999, 50.0, 1000 */
+int rcn_twoview_init(rcn_ctx *ctx, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
+                     const double *intr6_1 /* n_pairs x 6 */, const double *intr6_2, const rcn_twoview_options *opt,
+                     double *E_out, double *pose34_out /* n_pairs x 12 */, uint8_t *mask_out, uint8_t *cheir_mask_out,
+                     int32_t *count_out /* n_pairs x 2 */, int32_t *iterations_out);
+
+/* Pairs given by image ids (host array, n_pairs x (a, b)), their entries taken on the device from the lists
+ * rcn_match_lists_upload left resident (the list (a, b), or (b, a) read backwards under mirror) and the coordinates of
+ * rcn_coords_upload, in ascending order of a's feature.  Every other pointer is in DEVICE memory.  Asynchronous on the ctx
+ * stream after two small host-to-device copies (the coordinates' slot table, the pairs' slots; both staged in the ctx): no
+ * host wait, no device-to-host copy and no allocation once the workspace is sized (by `capacity` and the pairs' feature
+ * counts).  off_dev (n_pairs + 1) receives the pairs' offsets; mask_dev / cheir_mask_dev / qt_dev ((feature of a, feature of
+ * b) per entry) hold `capacity` entries; a pair whose entries would pass `capacity`, or that has no list, gets none and count
+ * -2.  qt_dev, E_dev, cheir_mask_dev, iterations_dev may be NULL.  RCN_ERR_ARG: no lists, a pair (a, a), a null pointer, bad
+ * options; RCN_ERR_NOT_FOUND: an image id that is not among the lists' images.  Entries of the resident lists whose
+ * features lie outside the coordinates are ignored; nothing is read or written out of bounds. */
+int rcn_twoview_init_device(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, const double *intr6_1_dev, const double *intr6_2_dev,
+                            const rcn_twoview_options *opt, int64_t capacity, int64_t *off_dev, int32_t *qt_dev, double *E_dev,
+                            double *pose34_dev, uint8_t *mask_dev, uint8_t *cheir_mask_dev, int32_t *count_dev, int32_t *iterations_dev);
+/* The camera block of rcn_ba_problem / rcn_ba_session_add_camera (angle-axis, translation) of rows of [R | t]: what
+ * rcn_ba_session_init_pair stores for the recovered pose, so that a caller who adds that camera itself gets the same bits.
+ * Pure host code, no ctx.  Domain: rotation angles away from pi (the axis is taken from R - R', divided by 2 sin(angle));
+ * below 1e-12 rad the axis is zero. */
+int rcn_pose34_to_pose6(const double *pose34, double *pose6_out);
+/* chooseInitialPair + triangulateInitialPair (:325-394) into an EMPTY session (RCN_ERR_ARG otherwise): rcn_twoview_init on the
+ * one pair, then -- when count_out[0] >= 0 -- camera 0 = the identity with intr6_1, camera 1 = the recovered pose with intr6_2,
+ * and EVERY entry of the pair (not the inliers only, as the reference) as a track of two observations through
+ * rcn_ba_session_triangulate with these two poses.  The same as rcn_twoview_init + rcn_pose34_to_pose6 +
+ * rcn_ba_session_add_camera twice + rcn_ba_session_triangulate on the same input, bit for bit.  count_out (2) is required;
+ * status_out (n bytes, the triangulation's), n_added_out and the other outputs may be NULL.  A negative count_out[0] leaves
+ * the session empty and returns RCN_OK. */
+int rcn_ba_session_init_pair(rcn_ba_session *s, int32_t n, const int32_t *xy1, const int32_t *xy2, const double *intr6_1,
+                             const double *intr6_2, const rcn_twoview_options *opt, double max_projection_error,
+                             double min_triangulation_angle, double *E_out, double *pose34_out, uint8_t *mask_out,
+                             uint8_t *cheir_mask_out, int32_t *count_out /* 2 */, int32_t *iterations_out, uint8_t *status_out,
+                             int32_t *n_added_out);
 
 /* ---- epipolar filter of a pair's matches --------------------------------------------------
  * GeometricFilter::estimateFundamental (GeometricFilter.cpp:39-61) as the pair loop uses it

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
     "rcn_landmark_attach", "rcn_ba_session_attach",
     "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
+    "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -97,6 +98,11 @@ class TriangulationProblem(C.Structure):
 class PnpOptions(C.Structure):
     _fields_ = [("max_projection_error", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int32),
                 ("refine_iterations", C.c_int32)]
+
+
+class TwoViewOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("distance_threshold", C.c_double),
+                ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
 class BaOptions(C.Structure):
@@ -312,6 +318,17 @@ def load():
     L.rcn_pnp_ransac_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, C.POINTER(PnpOptions), vp, vp, vp, vp, vp]
     L.rcn_ba_session_pnp.restype = C.c_int
     L.rcn_ba_session_pnp.argtypes = [vp, i32, vp, vp, vp, C.POINTER(PnpOptions), vp, vp, C.POINTER(i32)]
+    L.rcn_twoview_default_options.restype = None
+    L.rcn_twoview_default_options.argtypes = [C.POINTER(TwoViewOptions)]
+    L.rcn_twoview_init.restype = C.c_int
+    L.rcn_twoview_init.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(TwoViewOptions), vp, vp, vp, vp, vp, vp]
+    L.rcn_twoview_init_device.restype = C.c_int
+    L.rcn_twoview_init_device.argtypes = [vp, i32, vp, vp, vp, C.POINTER(TwoViewOptions), i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rcn_pose34_to_pose6.restype = C.c_int
+    L.rcn_pose34_to_pose6.argtypes = [vp, vp]
+    L.rcn_ba_session_init_pair.restype = C.c_int
+    L.rcn_ba_session_init_pair.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(TwoViewOptions), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp,
+                                           C.POINTER(i32)]
     L.rcn_store_save.restype = C.c_int
     L.rcn_store_save.argtypes = [C.c_char_p, C.POINTER(StoreContents)]
     L.rcn_store_open.restype = C.c_int

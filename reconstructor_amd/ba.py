@@ -258,6 +258,31 @@ class BaSession:
                                                        pose.ctypes.data, mask.ctypes.data, C.byref(cnt)))
         return pose, mask[:n], cnt.value
 
+    def init_pair(self, xy1, xy2, intr6_1, intr6_2, options=None, max_err=4.0, min_angle=1.0):
+        """chooseInitialPair + triangulateInitialPair into this (empty) session (rcn_ba_session_init_pair): the two-view search
+        on the pair's entries (integer pixels in ascending query-feature order), cameras 0 (the identity) and 1 (the
+        recovered pose), every entry triangulated as a two-observation track.  Returns twoview.two_view_init's dict for the
+        one pair plus status (the triangulation's, per entry) and added; count[0] < 0: no pose, the session stays empty."""
+        xy1 = np.ascontiguousarray(xy1, np.int32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.int32).reshape(-1, 2)
+        K1 = np.ascontiguousarray(intr6_1, np.float64).reshape(6)
+        K2 = np.ascontiguousarray(intr6_2, np.float64).reshape(6)
+        n = len(xy1)
+        if len(xy2) != n:
+            raise ValueError("init_pair: xy1 and xy2 differ in length")
+        out = dict(E=np.zeros(9), pose34=np.zeros(12), mask=np.zeros(max(n, 1), np.uint8), cheir_mask=np.zeros(max(n, 1), np.uint8),
+                   count=np.zeros(2, np.int32), iterations=np.zeros(1, np.int32), status=np.zeros(max(n, 1), np.uint8))
+        added = C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_init_pair(self.h, n, xy1.ctypes.data if n else None, xy2.ctypes.data if n else None,
+                                                             K1.ctypes.data, K2.ctypes.data, C.byref(options) if options is not None else None,
+                                                             float(max_err), float(min_angle), out["E"].ctypes.data, out["pose34"].ctypes.data,
+                                                             out["mask"].ctypes.data, out["cheir_mask"].ctypes.data, out["count"].ctypes.data,
+                                                             out["iterations"].ctypes.data, out["status"].ctypes.data, C.byref(added)))
+        for k in ("mask", "cheir_mask", "status"):
+            out[k] = out[k][:n]
+        out["added"] = added.value
+        return out
+
     def remove_outliers(self):
         npts = self.counts()[1]
         new_idx = np.zeros(max(1, npts), np.int32)

@@ -493,4 +493,47 @@ int rcn_ba_session_pnp(rcn_ba_session *s, int32_t n, const int32_t *landmark, co
                             static_cast<const double *>(s->pts.p), intr6, opt, pose34_out, nullptr, mask_out, count_out, nullptr);
 }
 
+// chooseInitialPair + triangulateInitialPair (:325-394) into an empty session: the search and the pose recovery of
+// twoview.hip, the two cameras (the identity, the recovered pose), then every match of the pair -- not the inliers only --
+// as a two-observation track through rcn_ba_session_triangulate.
+int rcn_ba_session_init_pair(rcn_ba_session *s, int32_t n, const int32_t *xy1, const int32_t *xy2, const double *intr6_1,
+                             const double *intr6_2, const rcn_twoview_options *opt, double max_projection_error,
+                             double min_triangulation_angle, double *E_out, double *pose34_out, uint8_t *mask_out,
+                             uint8_t *cheir_mask_out, int32_t *count_out, int32_t *iterations_out, uint8_t *status_out,
+                             int32_t *n_added_out)
+{
+    if (!s || n < 0 || !intr6_1 || !intr6_2 || !count_out || (n > 0 && (!xy1 || !xy2))) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    double pose34[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::vector<uint8_t> mask((size_t)std::max(n, 1));
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (!s->poses.empty() || !s->tracks.empty()) { ctx->set_error("rcn_ba_session_init_pair: the session is not empty"); return RCN_ERR_ARG; }
+        const int64_t off[2] = {0, n};
+        int rc = rcn_int_twoview_host(ctx, "rcn_ba_session_init_pair", 1, off, xy1, xy2, intr6_1, intr6_2, opt, E_out, pose34 + 12,
+                                      mask_out ? mask_out : mask.data(), cheir_mask_out, count_out, iterations_out);
+        if (rc) return rc;
+        if (pose34_out) std::copy(pose34 + 12, pose34 + 24, pose34_out);
+        if (n_added_out) *n_added_out = 0;
+        if (count_out[0] < 0) return RCN_OK;                // no pose: the session stays empty
+        double pose6[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        rcn_pose34_to_pose6(pose34 + 12, pose6 + 6);
+        // the two cameras under the same lock as the emptiness check (rcn_ba_session_add_camera's body, twice)
+        s->poses.insert(s->poses.end(), pose6, pose6 + 12);
+        s->intr.insert(s->intr.end(), intr6_1, intr6_1 + 6);
+        s->intr.insert(s->intr.end(), intr6_2, intr6_2 + 6);
+        s->version += 2;
+    }
+    std::vector<int32_t> off((size_t)n + 1), cam(2 * (size_t)n), xy(4 * (size_t)n);
+    for (int32_t e = 0; e < n; ++e) {
+        off[e] = 2 * e;
+        cam[2 * (size_t)e] = 0; cam[2 * (size_t)e + 1] = 1;
+        xy[4 * (size_t)e] = xy1[2 * (size_t)e]; xy[4 * (size_t)e + 1] = xy1[2 * (size_t)e + 1];
+        xy[4 * (size_t)e + 2] = xy2[2 * (size_t)e]; xy[4 * (size_t)e + 3] = xy2[2 * (size_t)e + 1];
+    }
+    off[n] = 2 * n;
+    return rcn_ba_session_triangulate(s, pose34, n, off.data(), cam.data(), xy.data(), max_projection_error, min_triangulation_angle,
+                                      status_out, nullptr, n_added_out);
+}
+
 }  // extern "C"

@@ -364,7 +364,138 @@ int corr_launch(rcn_ctx *ctx, const char *who, int32_t n_points, int32_t n_obs, 
     return RCN_OK;
 }
 
+// ---- a pair's entries in ascending query order, from the resident lists (rcn_twoview_init_device) -------------------------
+//   F1 k_pair_mark     one workgroup per pair (a, b): the list (a, b), or (b, a) read backwards under mirror, scattered into
+//                      a row over a's features: mark[f] = g (one writer per word: the list is injective), then the row counted
+//   F2 k_pair_offsets  one thread: the pairs' offsets; a pair whose entries would pass `capacity` gets none
+//   F3 k_pair_fill     one workgroup per pair: ordered compaction of the row (ballot prefix per wave, wave totals through
+//                      LDS) into the pixels of both sides and, when asked, the (f, g) themselves
+struct PairFill { int32_t sa, sb; int64_t woff; };      // slots of a and b, first word of the pair's row of mark
+
+__global__ __launch_bounds__(CB) void k_pair_mark(const PairFill *__restrict__ pf, const int2 *__restrict__ ent,
+                                                  const int64_t *__restrict__ list_off, const int32_t *__restrict__ dir, int32_t n_slots,
+                                                  const SlotDev *__restrict__ slots, int32_t *__restrict__ mark, int32_t *__restrict__ cnt)
+{
+    __shared__ int32_t red[CB / 64];
+    const int p = blockIdx.x, t = threadIdx.x;
+    const PairFill q = pf[p];
+    const int Ka = slots[q.sa].K, Kb = slots[q.sb].K;
+    int32_t *row = mark + q.woff;
+    const int d = dir[(size_t)q.sa * n_slots + q.sb];
+    if (d >= 0) {                                        // uniform over the workgroup
+        const bool back = d & 1;
+        const int64_t e0 = list_off[d >> 1], e1 = list_off[(d >> 1) + 1];
+        for (int64_t e = e0 + t; e < e1; e += CB) {
+            const int2 m = ent[e];
+            const int f = back ? m.y : m.x, g = back ? m.x : m.y;
+            if (f < 0 || f >= Ka || g < 0 || g >= Kb) continue;
+            row[f] = g;
+        }
+    }
+    __syncthreads();                                     // the row is read back by this workgroup only
+    int n = 0;
+    for (int f = t; f < Ka; f += CB) n += row[f] >= 0;
+    for (int s = 32; s; s >>= 1) n += __shfl_down(n, s);
+    if ((t & 63) == 0) red[t >> 6] = n;
+    __syncthreads();
+    if (t == 0) cnt[p] = red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ void k_pair_offsets(int32_t *__restrict__ cnt, int n_pairs, int64_t capacity, int64_t *__restrict__ off)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t s = 0;
+    off[0] = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        int64_t c = cnt[p];
+        if (s + c > capacity) { c = 0; cnt[p] = 0; }     // no room: the pair gets no entries
+        s += c;
+        off[p + 1] = s;
+    }
+}
+
+__global__ __launch_bounds__(CB) void k_pair_fill(const PairFill *__restrict__ pf, const SlotDev *__restrict__ slots,
+                                                  const int32_t *__restrict__ mark, const int32_t *__restrict__ cnt,
+                                                  const int64_t *__restrict__ off, int32_t *__restrict__ xy1, int32_t *__restrict__ xy2,
+                                                  int32_t *__restrict__ qt)
+{
+    __shared__ int32_t wtot[CB / 64];
+    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (cnt[p] <= 0) return;                             // uniform
+    const PairFill q = pf[p];
+    const SlotDev sa = slots[q.sa], sb = slots[q.sb];
+    const int32_t *row = mark + q.woff;
+    int64_t run = off[p];
+    const int64_t end = off[p + 1];
+    for (int f0 = 0; f0 < sa.K; f0 += CB) {
+        const int f = f0 + t;
+        const int g = f < sa.K ? row[f] : -1;
+        const unsigned long long b = __ballot(g >= 0);
+        if (lane == 0) wtot[wv] = (int32_t)__popcll(b);
+        __syncthreads();
+        int64_t pos = run + (int64_t)__popcll(b & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wv; ++w) pos += wtot[w];
+        if (g >= 0 && pos < end) {
+            xy1[2 * pos] = sa.xy[2 * (size_t)f]; xy1[2 * pos + 1] = sa.xy[2 * (size_t)f + 1];
+            xy2[2 * pos] = sb.xy[2 * (size_t)g]; xy2[2 * pos + 1] = sb.xy[2 * (size_t)g + 1];
+            if (qt) { qt[2 * pos] = f; qt[2 * pos + 1] = g; }
+        }
+        run += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        __syncthreads();
+    }
+}
+
 }  // namespace
+
+// rcn_twoview_init_device's front half, with ctx->mu held: the entries of n_pairs directed pairs (host array of image ids)
+// in ascending order of the first image's feature, pair p at off_dev[p] .. off_dev[p + 1] of xy1_dev / xy2_dev / qt_dev
+// (qt_dev may be NULL), `capacity` entries of room.  Only enqueues.  A pair without a list gets no entries.
+int rcn_int_pair_fill(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int32_t *pairs, int64_t capacity, int64_t *off_dev,
+                      int32_t *xy1_dev, int32_t *xy2_dev, int32_t *qt_dev)
+{
+    CorrLists &L = ctx->corr;
+    if (!L.live) { ctx->set_error(std::string(who) + ": no match lists (rcn_match_lists_upload)"); return RCN_ERR_ARG; }
+    hipStream_t st = ctx->stream;
+    if (n_pairs == 0) { RCN_HIP(hipMemsetAsync(off_dev, 0, 8, st)); return RCN_OK; }
+    if (!ctx->tv_ev && hipEventCreateWithFlags(&ctx->tv_ev, hipEventDisableTiming) != hipSuccess) { ctx->tv_ev = nullptr; RCN_HIP(hipGetLastError()); }
+    if (ctx->tv_stage_pending) { RCN_HIP(hipEventSynchronize(ctx->tv_ev)); ctx->tv_stage_pending = false; }    // the staging buffer is free again
+    ctx->tv_stage_host.resize((size_t)n_pairs * sizeof(PairFill));
+    PairFill *pf = reinterpret_cast<PairFill *>(ctx->tv_stage_host.data());
+    int64_t sum_ka = 0;
+    for (int32_t p = 0; p < n_pairs; ++p) {
+        int32_t sl[2];
+        for (int k = 0; k < 2; ++k) {
+            const int32_t id = pairs[2 * p + k];
+            auto it = std::lower_bound(L.ids.begin(), L.ids.end(), id);
+            if (it == L.ids.end() || *it != id) { ctx->set_error(std::string(who) + ": image " + std::to_string(id) + " is not among the resident lists' images"); return RCN_ERR_NOT_FOUND; }
+            sl[k] = (int32_t)(it - L.ids.begin());
+        }
+        if (sl[0] == sl[1]) { ctx->set_error(std::string(who) + ": pair (" + std::to_string(pairs[2 * p]) + ", " + std::to_string(pairs[2 * p]) + ") pairs an image with itself"); return RCN_ERR_ARG; }
+        auto ca = ctx->coords.find(pairs[2 * p]);
+        if (ca == ctx->coords.end()) { ctx->set_error(std::string(who) + ": coordinates of image " + std::to_string(pairs[2 * p]) + " are no longer resident"); return RCN_ERR_ARG; }
+        pf[p].sa = sl[0]; pf[p].sb = sl[1]; pf[p].woff = sum_ka;
+        sum_ka += ca->second.second;
+    }
+    int64_t sum_k = 0;
+    int rc = refresh_slots(ctx, who, &sum_k);
+    if (rc) return rc;
+    const size_t np = (size_t)n_pairs;
+    const size_t b_pf = al256(np * sizeof(PairFill)), b_cnt = al256(4 * np), b_mark = al256(4 * (size_t)std::max<int64_t>(sum_ka, 1));
+    RCN_HIP(ctx->tv_fws.reserve(b_pf + b_cnt + b_mark));
+    char *w = ctx->tv_fws.as<char>();
+    PairFill *d_pf = reinterpret_cast<PairFill *>(w);
+    int32_t *d_cnt = reinterpret_cast<int32_t *>(w + b_pf), *d_mark = reinterpret_cast<int32_t *>(w + b_pf + b_cnt);
+    RCN_HIP(hipMemcpyAsync(d_pf, pf, np * sizeof(PairFill), hipMemcpyHostToDevice, st));
+    RCN_HIP(hipEventRecord(ctx->tv_ev, st));
+    ctx->tv_stage_pending = true;
+    RCN_HIP(hipMemsetAsync(d_mark, 0xFF, b_mark, st));
+    const SlotDev *slots = ctx->corr_slots.as<SlotDev>();
+    k_pair_mark<<<(unsigned)n_pairs, CB, 0, st>>>(d_pf, L.ent.as<int2>(), L.list_off.as<int64_t>(), L.dir.as<int32_t>(), (int32_t)L.ids.size(), slots, d_mark, d_cnt);
+    k_pair_offsets<<<1, 64, 0, st>>>(d_cnt, n_pairs, capacity, off_dev);
+    k_pair_fill<<<(unsigned)n_pairs, CB, 0, st>>>(d_pf, slots, d_mark, d_cnt, off_dev, xy1_dev, xy2_dev, qt_dev);
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
 
 extern "C" {
 

@@ -12,9 +12,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.6 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.7 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.6 (gfx950)";
+    return "reconstructor_amd 0.7 (gfx950)";
 #endif
 }
 
@@ -214,6 +214,8 @@ void rcn_destroy(rcn_ctx *ctx)
     ctx->corr_ws.release(); ctx->corr_hws.release(); ctx->corr_slots.release(); ctx->att_ws.release();
     if (ctx->corr_ev) (void)hipEventDestroy(ctx->corr_ev);
     ctx->pnp_hws.release(); ctx->pnp_slots.release();
+    ctx->tv_hws.release(); ctx->tv_dws.release(); ctx->tv_fws.release();
+    if (ctx->tv_ev) (void)hipEventDestroy(ctx->tv_ev);
     if (ctx->pnp_ev) (void)hipEventDestroy(ctx->pnp_ev);
     if (ctx->ev_made) {
         for (auto &call : ctx->ev_c)

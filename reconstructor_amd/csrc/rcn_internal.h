@@ -224,6 +224,10 @@ struct rcn_ctx {
     std::vector<char> pnp_slots_host;   // staging of pnp_slots (uploaded asynchronously; pnp_ev marks the copy)
     hipEvent_t pnp_ev = nullptr;
     bool pnp_slots_pending = false;
+    DevBuf tv_hws, tv_dws, tv_fws;      // two-view initialisation (twoview.hip): host-API staging and workspace, workspace of the device entry, of its fill (corr2d3d.hip)
+    std::vector<char> tv_stage_host;    // staging of the device entry's pair table (uploaded asynchronously; tv_ev marks the copy)
+    hipEvent_t tv_ev = nullptr;
+    bool tv_stage_pending = false;
     int64_t corr_budget = 1ll << 30;    // bytes of hit rows per batch (rcn_corr_set_workspace_bytes)
     std::vector<int> ba_graph_cam, ba_graph_pt;     // observation graph of the last plain rcn_ba_solve (host copy): an identical graph reuses the pair lists
     int ba_graph_nc = 0, ba_graph_np = 0;
@@ -305,6 +309,13 @@ int rcn_int_pnp_host(rcn_ctx *ctx, const char *who, int32_t n_views, const int64
                      int32_t n_points, const double *points_host, const double *points_dev, const double *intr6,
                      const rcn_pnp_options *opt, double *pose34_out, double *ransac_pose34_out, uint8_t *mask_out,
                      int32_t *count_out, int32_t *iterations_out);
+// twoview.hip: rcn_twoview_init with ctx->mu held (rcn_ba_session_init_pair)
+int rcn_int_twoview_host(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
+                         const double *intr6_1, const double *intr6_2, const rcn_twoview_options *opt, double *E_out,
+                         double *pose34_out, uint8_t *mask_out, uint8_t *cheir_mask_out, int32_t *count_out, int32_t *iterations_out);
+// corr2d3d.hip, with ctx->mu held: the entries of directed pairs from the resident lists, ascending query order (rcn_twoview_init_device)
+int rcn_int_pair_fill(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int32_t *pairs, int64_t capacity, int64_t *off_dev,
+                      int32_t *xy1_dev, int32_t *xy2_dev, int32_t *qt_dev);
 // corr2d3d.hip, with ctx->mu held: step 1 of triangulateMatchedLandmarks on device arrays (rcn_ba_session_attach)
 int rcn_int_attach_check(rcn_ctx *ctx, const char *who, int32_t n_points, int32_t n, const int32_t *lm, const int32_t *feat, int32_t *n_feat);
 size_t rcn_int_attach_ws_bytes(int32_t n_feat);

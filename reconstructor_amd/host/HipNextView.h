@@ -1,4 +1,4 @@
-// HipNextView.h -- SequentialReconstructor::calc2d3dMatches, ::rankNextImages, ::registerImagePnP and step 1 of
+// HipNextView.h -- SequentialReconstructor::chooseInitialPair, ::calc2d3dMatches, ::rankNextImages, ::registerImagePnP and step 1 of
 // ::triangulateMatchedLandmarks (SequentialReconstructor.cpp:643-695, :697-759, :559-638, :497-512) over the reference's own
 // containers, with the search handed to rcn_corr_2d3d, the pose to rcn_pnp_ransac and the attach rules to rcn_landmark_attach
 // (include/rcn.h).
@@ -130,6 +130,53 @@ public:
         } else {
             throw std::runtime_error("Wrong next image ranking mode!");
         }
+    }
+
+    // SequentialReconstructor::chooseInitialPair (:325-375) through rcn_twoview_init: the pair with the most matches (the
+    // lexicographically first (i, j) among equals -- the reference's choice among equals is an accident of an unordered_map
+    // and an unstable sort), its matches in ascending order of the first image's feature, cv::findEssentialMat's and
+    // cv::recoverPose's defaults.  Returns the 4 x 4 pose of the second image relative to the first (|t| = 1); throws when
+    // there are no matches or no model.  inlierMatchIds (may be NULL): one flag per match in that order.
+    template <class Pose4 = Mat4d, class FeatureMatches>
+    Pose4 chooseInitialPair(int &imgIdx1, int &imgIdx2, std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                            const FeatureMatches &featureMatches, std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics,
+                            std::vector<bool> *inlierMatchIds = nullptr)
+    {
+        bool have = false;
+        size_t bestN = 0;
+        std::pair<int, int> best{0, 0};
+        for (const auto &[key, m] : featureMatches) {
+            const std::pair<int, int> k(key.first, key.second);
+            if (!have || m.size() > bestN || (m.size() == bestN && k < best)) { have = true; bestN = m.size(); best = k; }
+        }
+        if (!have) throw std::runtime_error("chooseInitialPair: no matches");
+        imgIdx1 = best.first; imgIdx2 = best.second;
+        std::vector<std::pair<int, int>> qt;
+        for (const auto &[key, m] : featureMatches)
+            if (key.first == best.first && key.second == best.second) qt.assign(m.begin(), m.end());
+        std::sort(qt.begin(), qt.end());
+        const size_t n = qt.size();
+        std::vector<int32_t> xy1(2 * n + 2), xy2(2 * n + 2);
+        for (size_t e = 0; e < n; ++e) {
+            const auto &a = features.at(imgIdx1).at(qt[e].first)->featCoord, &b = features.at(imgIdx2).at(qt[e].second)->featCoord;
+            xy1[2 * e] = a.x; xy1[2 * e + 1] = a.y; xy2[2 * e] = b.x; xy2[2 * e + 1] = b.y;
+        }
+        const PinholeCamera &k1 = imgIdx2camIntrinsics.at(imgIdx1), &k2 = imgIdx2camIntrinsics.at(imgIdx2);
+        const double K1[6] = {k1.fX, k1.fY, k1.cX, k1.cY, k1.k1, k1.k2}, K2[6] = {k2.fX, k2.fY, k2.cX, k2.cY, k2.k1, k2.k2};
+        const int64_t off[2] = {0, (int64_t)n};
+        double P[12];
+        std::vector<uint8_t> mask(n + 1);
+        int32_t count[2] = {0, 0};
+        check(rcn_twoview_init(ctx_, 1, off, xy1.data(), xy2.data(), K1, K2, nullptr, nullptr, P, mask.data(), nullptr, count, nullptr),
+              "rcn_twoview_init");
+        if (count[0] < 0)
+            throw std::runtime_error("chooseInitialPair: no pose for the pair (" + std::to_string(imgIdx1) + ", " + std::to_string(imgIdx2) +
+                                     (count[0] == -2 ? ") (fewer than 5 matches)" : ") (no model)"));
+        if (inlierMatchIds) { inlierMatchIds->clear(); for (size_t e = 0; e < n; ++e) inlierMatchIds->push_back(mask[e] != 0); }
+        Pose4 T;
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T(r, c) = r == c ? 1.0 : 0.0;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T(r, c) = P[4 * r + c];
+        return T;
     }
 
     // :559-638.  maxProjectionError is the threshold (:596), confidence 0.99 and 10000 iterations as the reference passes them.
