@@ -87,6 +87,41 @@ int rcn_desc_sample_device(rcn_ctx *ctx, const float *desc_map_dev, int64_t stri
  * written as zeros and counted.  rcn_desc_sample_errors waits for the ctx stream and returns RCN_ERR_ARG (count in
  * *n_out_of_range, may be NULL) when any keypoint of the calls since the last read was outside; the count is cleared. */
 int rcn_desc_sample_errors(rcn_ctx *ctx, int32_t *n_out_of_range);
+/* The same for n images in one launch: map i at desc_maps_dev + i * stride_img, keypoints kp_xy_dev[i][K][2], rows
+ * out_rows_dev[i][K][D].  The first min(counts_dev[i], K) rows of image i are bit-identical to rcn_desc_sample_device;
+ * the rows past them are written as zeros (the local_K contract of rcn_shard_exchange) and are NOT counted as
+ * out-of-map errors, whatever their coordinates hold (rcn_kp_detect_device pads with (-1, -1)). */
+int rcn_desc_sample_batch_device(rcn_ctx *ctx, const float *desc_maps_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                                 int32_t Hc, int32_t Wc, const int32_t *kp_xy_dev /*[n][K][2]*/, const int32_t *counts_dev /*[n]*/,
+                                 int32_t n, int32_t K, int32_t D, float *out_rows_dev /*[n][K][D]*/);
+
+/* ---- keypoints ---------------------------------------------------
+ * processKeypoints of the reference (FeatureSuperPoint.cpp:145-179) for n images per call: heat map from the network's
+ * [65][H/8][W/8] logits, threshold, nmsFast, border filter; all in HBM, asynchronous on the ctx stream.
+ *   logits: element strides as in rcn_desc_sample_device -- NCHW is (65*Hc*Wc, Hc*Wc, Wc, 1), NHWC (Hc*Wc*65, 1, Wc*65, 65).
+ *   heat_mode: RCN_KP_HEAT_REFERENCE is extractHeatMap as written (each plane row divided by the sum of the plane as
+ *   modified so far, + 1e-5); RCN_KP_HEAT_SOFTMAX is the softmax over the 65 channels of a cell.  Channel 64 is dropped
+ *   and heat[8 yc + c / 8][8 xc + c % 8] = h[c][yc][xc].  This stage carries a tolerance (expf); the rest is exact.
+ *   A pixel is a candidate iff (double)heat >= conf_thresh (never a NaN).  Canonical order: confidence descending, then
+ *   raster index y * W + x ascending (std::stable_sort on the reference's raster-ordered input).  nmsFast with
+ *   distThresh = nms_radius in that order; then keypoints with x < border || x >= W - border || y < border ||
+ *   y >= H - border are dropped.  Output in raster order; counts_dev[i] is the number of survivors; when it exceeds K
+ *   the K first of the canonical order are emitted (still in raster order).  Rows past min(counts[i], K): xy (-1, -1),
+ *   conf 0.  heat_out_dev receives the dense heat maps, rounds_dev the rounds of the NMS iteration per image.
+ * RCN_ERR_ARG: H or W no positive multiple of 8 (rcn_kp_nms_device: not positive), H * W > 2^31 - 1, n < 0, K < 1,
+ * nms_radius outside 0..8, border < 0, unknown mode, null required pointer.  n == 0 launches nothing. */
+#define RCN_KP_HEAT_REFERENCE 0
+#define RCN_KP_HEAT_SOFTMAX   1
+/* bytes of LDS the NMS kernel may use for its status map (2 bits per pixel): images of up to 4 * this many pixels keep
+ * the map in LDS, larger ones in HBM */
+#define RCN_KP_LDS_STATUS_BYTES 131072
+int rcn_kp_detect_device(rcn_ctx *ctx, const float *logits_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                         int32_t n, int32_t H, int32_t W, int32_t heat_mode, double conf_thresh, int32_t nms_radius, int32_t border,
+                         int32_t K, int32_t *kp_xy_dev /*[n][K][2]*/, float *conf_dev /*[n][K], may be NULL*/,
+                         int32_t *counts_dev /*[n]*/, float *heat_out_dev /*[n][H][W], may be NULL*/, int32_t *rounds_dev /*[n], may be NULL*/);
+/* The exact stages alone (threshold, NMS, border, cap) on heat maps the caller already has, [n][H][W] fp32. */
+int rcn_kp_nms_device(rcn_ctx *ctx, const float *heat_dev /*[n][H][W]*/, int32_t n, int32_t H, int32_t W, double conf_thresh,
+                      int32_t nms_radius, int32_t border, int32_t K, int32_t *kp_xy_dev, float *conf_dev, int32_t *counts_dev, int32_t *rounds_dev);
 /* Host-side batch ingest: n_images images with their own row counts K[i] >= 0, each a dense row-major K[i] x D
  * fp32 matrix in HOST memory (rows[i]; what featDescToCV packs per call, FeatureMatcher.cpp:11-25 -- here for every
  * image of the loop at once), become ids first_img_id .. first_img_id + n_images - 1.  One device block of

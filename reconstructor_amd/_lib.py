@@ -17,7 +17,7 @@ ERRORS = {-1: "RCN_ERR_ARG", -2: "RCN_ERR_HIP", -3: "RCN_ERR_NO_DEVICE",
 # every symbol include/rcn.h declares (tests check the library exports exactly these)
 SYMBOLS = [
     "rcn_create", "rcn_destroy", "rcn_last_error", "rcn_version", "rcn_set_stream",
-    "rcn_synchronize", "rcn_desc_upload", "rcn_desc_upload_device", "rcn_desc_upload_batch_device", "rcn_desc_upload_batch", "rcn_desc_remove", "rcn_desc_sample_device", "rcn_desc_sample_errors", "rcn_desc_clear",
+    "rcn_synchronize", "rcn_desc_upload", "rcn_desc_upload_device", "rcn_desc_upload_batch_device", "rcn_desc_upload_batch", "rcn_desc_remove", "rcn_desc_sample_device", "rcn_desc_sample_errors", "rcn_desc_sample_batch_device", "rcn_desc_clear",
     "rcn_desc_count", "rcn_match_pair", "rcn_match_grid", "rcn_match_grid_device",
     "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_factor_plan",
     "rcn_landmark_validity", "rcn_landmark_validity_device",
@@ -37,6 +37,7 @@ SYMBOLS = [
     "rcn_landmark_attach", "rcn_ba_session_attach",
     "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
     "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
+    "rcn_kp_detect_device", "rcn_kp_nms_device",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -178,6 +179,12 @@ def load():
     L.rcn_desc_sample_device.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, i32, i32, vp]
     L.rcn_desc_sample_errors.restype = C.c_int
     L.rcn_desc_sample_errors.argtypes = [vp, C.POINTER(i32)]
+    L.rcn_desc_sample_batch_device.restype = C.c_int
+    L.rcn_desc_sample_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, vp, vp, i32, i32, i32, vp]
+    L.rcn_kp_detect_device.restype = C.c_int
+    L.rcn_kp_detect_device.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.rcn_kp_nms_device.restype = C.c_int
+    L.rcn_kp_nms_device.argtypes = [vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp]
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

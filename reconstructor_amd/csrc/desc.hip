@@ -16,9 +16,11 @@
 namespace {
 
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(256) void k_desc_sample(const float *__restrict__ map, long long sc, long long sy, long long sx,
-                                                     int Hc, int Wc, const int32_t *__restrict__ kp, int K, int D,
-                                                     float *__restrict__ out, unsigned *__restrict__ n_bad)
+// Four keypoints per workgroup, one wavefront each.  Rows Kv <= k < K (past an image's keypoint count, batch entry) are
+// zeros and read nothing, their coordinates included.
+__device__ __forceinline__ void desc_sample_rows(const float *__restrict__ map, long long sc, long long sy, long long sx,
+                                                 int Hc, int Wc, const int32_t *__restrict__ kp, int Kv, int K, int D,
+                                                 float *__restrict__ out, unsigned *__restrict__ n_bad)
 {
     __shared__ float sq[4][256 + 8];
     __shared__ double nrm[4];
@@ -27,7 +29,7 @@ __global__ __launch_bounds__(256) void k_desc_sample(const float *__restrict__ m
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     const float *base = nullptr;
     bool inside = false;
-    if (k < K) {
+    if (k < Kv) {
         // a keypoint outside the map (the reference's tensor indexing would throw there): nothing is read, the row
         // comes out as zeros and the call is counted in *n_bad (rcn_desc_sample_errors)
         const int x = kp[2 * k], y = kp[2 * k + 1];
@@ -60,6 +62,23 @@ __global__ __launch_bounds__(256) void k_desc_sample(const float *__restrict__ m
     }
 }
 
+__global__ __launch_bounds__(256) void k_desc_sample(const float *__restrict__ map, long long sc, long long sy, long long sx,
+                                                     int Hc, int Wc, const int32_t *__restrict__ kp, int K, int D,
+                                                     float *__restrict__ out, unsigned *__restrict__ n_bad)
+{
+    desc_sample_rows(map, sc, sy, sx, Hc, Wc, kp, K, K, D, out, n_bad);
+}
+
+// blockIdx.y = image: its own map, keypoints, count and rows
+__global__ __launch_bounds__(256) void k_desc_sample_batch(const float *__restrict__ maps, long long si, long long sc, long long sy, long long sx,
+                                                           int Hc, int Wc, const int32_t *__restrict__ kp, const int32_t *__restrict__ counts,
+                                                           int K, int D, float *__restrict__ out, unsigned *__restrict__ n_bad)
+{
+    const int img = blockIdx.y;
+    desc_sample_rows(maps + (long long)img * si, sc, sy, sx, Hc, Wc, kp + (size_t)img * K * 2, max(0, min(counts[img], K)), K, D,
+                     out + (size_t)img * K * D, n_bad);
+}
+
 }  // namespace
 
 extern "C" int rcn_desc_sample_device(rcn_ctx *ctx, const float *desc_map_dev, int64_t stride_c, int64_t stride_y, int64_t stride_x,
@@ -79,6 +98,29 @@ extern "C" int rcn_desc_sample_device(rcn_ctx *ctx, const float *desc_map_dev, i
     }
     k_desc_sample<<<(K + 3) / 4, 256, 0, ctx->stream>>>(desc_map_dev, stride_c, stride_y, stride_x, Hc, Wc, kp_xy_dev, K, D, out_rows_dev,
                                                         ctx->desc_bad.as<unsigned>());
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
+
+extern "C" int rcn_desc_sample_batch_device(rcn_ctx *ctx, const float *desc_maps_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y,
+                                            int64_t stride_x, int32_t Hc, int32_t Wc, const int32_t *kp_xy_dev, const int32_t *counts_dev,
+                                            int32_t n, int32_t K, int32_t D, float *out_rows_dev)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (n < 0 || n > 65535 || K < 0 || D < 1 || D > 256 || Hc < 1 || Wc < 1 ||
+        (n > 0 && K > 0 && (!desc_maps_dev || !kp_xy_dev || !counts_dev || !out_rows_dev))) {
+        ctx->set_error("rcn_desc_sample_batch_device: bad argument (1 <= D <= 256, n <= 65535)");
+        return RCN_ERR_ARG;
+    }
+    if (n == 0 || K == 0) return RCN_OK;
+    RCN_HIP(hipSetDevice(ctx->device));
+    if (!ctx->desc_bad.p) {
+        RCN_HIP(ctx->desc_bad.reserve(sizeof(unsigned)));
+        RCN_HIP(hipMemsetAsync(ctx->desc_bad.p, 0, sizeof(unsigned), ctx->stream));
+    }
+    k_desc_sample_batch<<<dim3((K + 3) / 4, n), 256, 0, ctx->stream>>>(desc_maps_dev, stride_img, stride_c, stride_y, stride_x, Hc, Wc, kp_xy_dev,
+                                                                       counts_dev, K, D, out_rows_dev, ctx->desc_bad.as<unsigned>());
     RCN_HIP(hipGetLastError());
     return RCN_OK;
 }

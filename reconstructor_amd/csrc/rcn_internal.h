@@ -153,6 +153,7 @@ struct rcn_ctx {
     double thr2 = 0.0;       // BIG-row threshold in force (part of the scale: a change reconverts everything)
     DevBuf scale_dev;        // one ScaleDev: what the kernels read
     DevBuf desc_bad;         // desc.hip: keypoints outside their descriptor map since the last rcn_desc_sample_errors
+    DevBuf kp_ws;            // keypoints.hip: candidate lists, heat map / status when the caller keeps neither, scale rows
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)

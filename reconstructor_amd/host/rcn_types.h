@@ -3,6 +3,7 @@
 // Same names and member names as the reference (namespace reconstructor::Core) so that the
 // adapters below read like the reference's own call sites:
 //   FeatCoord / FeatDesc / Feature / FeaturePtr   datatypes.h:10-107
+//   FeatCoordConf / FeatureConf                   datatypes.h:30-44, 112-136 (SuperPoint: a confidence per keypoint)
 //   TriangulatedFeature / Landmark                datatypes.h:125-183
 //   PinholeCamera                                 Camera.h:12-120 (fX,fY,cX,cY,k1,k2 + project)
 // Only the members the matcher / bundle-adjuster boundary touches are declared.
@@ -22,6 +23,12 @@ template <typename coordType = int> struct FeatCoord {
     coordType x{}, y{};
 };
 
+template <typename coordType = int> struct FeatCoordConf : FeatCoord<coordType> {
+    FeatCoordConf() = default;
+    FeatCoordConf(coordType x_, coordType y_, double conf_) : FeatCoord<coordType>(x_, y_), conf(conf_) {}
+    double conf = 0.01;
+};
+
 struct FeatDesc {
     FeatDesc() = default;
     template <typename It> FeatDesc(It first, It last) : desc(first, last) {}
@@ -36,6 +43,12 @@ template <typename coordType = int> struct Feature {
     int landmarkId = -1;
 };
 template <typename coordType = int> using FeaturePtr = std::shared_ptr<Feature<coordType>>;
+
+template <typename coordType = int> struct FeatureConf : Feature<coordType> {
+    FeatureConf() = default;
+    FeatureConf(FeatCoordConf<coordType> c, FeatDesc d) : Feature<coordType>(static_cast<FeatCoord<coordType>>(c), std::move(d)), conf(c.conf) {}
+    double conf = 0.0;
+};
 
 struct TriangulatedFeature {
     TriangulatedFeature() = default;
