@@ -48,9 +48,9 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
  * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
- * initialisation entry points and rcn_twoview_options).
+ * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 7
+#define RCN_ABI_REVISION 8
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -122,6 +122,68 @@ int rcn_kp_detect_device(rcn_ctx *ctx, const float *logits_dev, int64_t stride_i
 /* The exact stages alone (threshold, NMS, border, cap) on heat maps the caller already has, [n][H][W] fp32. */
 int rcn_kp_nms_device(rcn_ctx *ctx, const float *heat_dev /*[n][H][W]*/, int32_t n, int32_t H, int32_t W, double conf_thresh,
                       int32_t nms_radius, int32_t border, int32_t K, int32_t *kp_xy_dev, float *conf_dev, int32_t *counts_dev, int32_t *rounds_dev);
+/* ---- SuperGlue's optimal-matching layer ----------------------------
+ * What FeatureMatcherSuperglue::matchFeatures (FeatureMatcherSuperglue.cpp:51-101) runs behind the graph network: the
+ * D-dimensional score matrix of the two sets of matching descriptors, the dustbin-augmented Sinkhorn iteration in the log
+ * domain, the mutual-argmax selection and the two thresholds (the network's match_threshold, the reference's
+ * matchScoreThreshold, :82).  B pairs per call, all in HBM, asynchronous on the ctx stream; the workspace (u, v, partial
+ * column sums, the scores of rcn_sg_match_device) belongs to the ctx and grows: no host synchronisation once it has its size.
+ *
+ * For one pair with m rows of image 0 and n rows of image 1 (alpha = the learned bin_score):
+ *   S[i][j] = (sum_d d0[i][d] d1[j][d]) / sqrt(D);  Z = S bordered by one row and one column of alpha (never materialised);
+ *   norm = -log(m + n), log_mu[i] = norm, log_mu[m] = log(n) + norm, log_nu[j] = norm, log_nu[n] = log(m) + norm;  u = v = 0;
+ *   `iterations` times: u[i] = log_mu[i] - logsumexp_j(Z[i][j] + v[j]), then v[j] = log_nu[j] - logsumexp_i(Z[i][j] + u[i]);
+ *   logP = Z + u + v - norm.  On the inner m x n block: i0[i] = argmax_j, i1[j] = argmax_i, ties to the LOWEST index; row i is
+ *   mutual iff i1[i0[i]] == i; mscores0[i] = exp(max_j logP[i][j]) if mutual else 0; matches0[i] = i0[i] if mutual and
+ *   mscores0[i] > match_threshold, else -1; matches1 / mscores1 the same through i1.  table[i] = matches0[i] if also
+ *   mscores0[i] > score_threshold, else -1: the std::map of the reference in the dense form of rcn_match_grid_device
+ *   (table_stride >= M, tail -1, counts[b] = entries kept), consumed as it is by rcn_match_compact_begin.
+ * All arithmetic is fp32 (expf / logf); the tolerance against the float64 statement is derived in DESIGN section 20.
+ *
+ * m_dev / n_dev: the pairs' counts in HBM (NULL: M resp. N for every pair); a count outside 0..M / 0..N is clamped on the
+ * device.  Rows and columns past a pair's counts are padding: never read; their outputs are -1 / 0 (logP_out: 0).  A pair
+ * with m == 0 or n == 0 runs no iteration and yields -1 / 0, count 0.  A pair whose final u or v holds a non-finite value
+ * (non-finite scores) yields -1 / 0, count 0 and status 1; every other pair status 0.
+ * logP_out: [B][M + 1][N + 1]; the dustbin row of a pair is row M, its dustbin column is column N, whatever m and n.
+ *
+ * Two device paths, chosen per pair from (m, n) and `path` alone, so that a pair's result never depends on its batch:
+ *   fused   (m + 1)(n + 1) floats fit RCN_SG_LDS_BYTES: one workgroup loads the matrix once and iterates out of LDS;
+ *   banded  otherwise: workgroups own bands of 8 rows; per iteration one sweep over the matrix (row logsumexp, and from the
+ *           same resident band the partial column (max, sum) pairs), then a small launch that merges the partials in band
+ *           order.  Pairs are processed in chunks whose matrices fit rcn_sg_set_chunk_bytes (cache residency; bytes <= 0:
+ *           no limit, the default); results do not depend on the chunk size.
+ * Each path is bit-reproducible; the two agree within the tolerance.  RCN_SG_PATH_FUSED is judged by the capacity: it
+ * needs (M + 1)(N + 1) floats to fit (the counts live on the device), RCN_ERR_UNSUPPORTED otherwise.
+ *
+ * Descriptors: fp32, addressed by element strides (pair, row, d): the network's [B][D][K] output (the reference's featDescs
+ * layout) is (D K, 1, K), row-major [B][K][D] is (K D, D, 1).  Products and sums in fp32, ascending d.
+ * RCN_ERR_ARG: null required pointer, B < 0, M < 1, N < 1, D < 1, table_stride < M, a table without counts,
+ * iterations < 0, a threshold outside [0, 1), non-finite alpha, unknown path.  RCN_ERR_UNSUPPORTED: M or N above
+ * RCN_SG_MAX_POINTS.  B == 0 launches nothing. */
+typedef struct { double alpha, match_threshold, score_threshold; int32_t iterations, path; } rcn_sg_options;
+#define RCN_SG_PATH_AUTO   0
+#define RCN_SG_PATH_FUSED  1
+#define RCN_SG_PATH_BANDED 2
+#define RCN_SG_LDS_BYTES  131072   /* a pair whose bordered matrix fits this many bytes of LDS takes the fused path */
+#define RCN_SG_MAX_POINTS 4096     /* largest M and N */
+void rcn_sg_default_options(rcn_sg_options *o);   /* alpha 1.0, thresholds 0.2 and 0.5, 100 iterations, RCN_SG_PATH_AUTO */
+int rcn_sg_scores_device(rcn_ctx *ctx, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
+                         const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                         const int32_t *m_dev /*[B] or NULL*/, const int32_t *n_dev /*[B] or NULL*/, int32_t B, int32_t M, int32_t N, int32_t D,
+                         float *scores_out_dev /*[B][M][N]; padding is not written*/);
+int rcn_sg_assign_device(rcn_ctx *ctx, const float *scores_dev, int64_t stride_pair, int64_t stride_row, int64_t stride_col,
+                         const int32_t *m_dev /*[B] or NULL = M*/, const int32_t *n_dev /*[B] or NULL = N*/, int32_t B, int32_t M, int32_t N,
+                         const rcn_sg_options *opt /*NULL = defaults*/, int32_t *matches0_dev /*[B][M]*/, int32_t *matches1_dev /*[B][N], may be NULL*/,
+                         float *mscores0_dev /*[B][M], may be NULL*/, float *mscores1_dev /*[B][N], may be NULL*/,
+                         int32_t *table_dev /*[B][table_stride], may be NULL*/, int64_t table_stride, int32_t *counts_dev /*[B], with table*/,
+                         float *logP_out_dev /*[B][M+1][N+1], may be NULL: diagnostics and tests*/, int32_t *status_dev /*[B], may be NULL*/);
+/* rcn_sg_scores_device into the ctx's workspace, then rcn_sg_assign_device on it: bit for bit the two calls. */
+int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
+                        const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                        const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
+                        int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
+                        int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev);
+int rcn_sg_set_chunk_bytes(rcn_ctx *ctx, int64_t bytes);
 /* Host-side batch ingest: n_images images with their own row counts K[i] >= 0, each a dense row-major K[i] x D
  * fp32 matrix in HOST memory (rows[i]; what featDescToCV packs per call, FeatureMatcher.cpp:11-25 -- here for every
  * image of the loop at once), become ids first_img_id .. first_img_id + n_images - 1.  One device block of

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
     "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
     "rcn_kp_detect_device", "rcn_kp_nms_device",
+    "rcn_sg_default_options", "rcn_sg_scores_device", "rcn_sg_assign_device", "rcn_sg_match_device", "rcn_sg_set_chunk_bytes",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -104,6 +105,11 @@ class PnpOptions(C.Structure):
 class TwoViewOptions(C.Structure):
     _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("distance_threshold", C.c_double),
                 ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SgOptions(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("match_threshold", C.c_double), ("score_threshold", C.c_double),
+                ("iterations", C.c_int32), ("path", C.c_int32)]
 
 
 class BaOptions(C.Structure):
@@ -185,6 +191,17 @@ def load():
     L.rcn_kp_detect_device.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp]
     L.rcn_kp_nms_device.restype = C.c_int
     L.rcn_kp_nms_device.argtypes = [vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp]
+    L.rcn_sg_default_options.restype = None
+    L.rcn_sg_default_options.argtypes = [C.POINTER(SgOptions)]
+    sg_out = [vp, vp, vp, vp, vp, i64, vp, vp, vp]      # matches0/1, mscores0/1, table, stride, counts, logP, status
+    L.rcn_sg_scores_device.restype = C.c_int
+    L.rcn_sg_scores_device.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, i32, i32, i32, i32, vp]
+    L.rcn_sg_assign_device.restype = C.c_int
+    L.rcn_sg_assign_device.argtypes = [vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, C.POINTER(SgOptions)] + sg_out
+    L.rcn_sg_match_device.restype = C.c_int
+    L.rcn_sg_match_device.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, i32, i32, i32, i32, C.POINTER(SgOptions)] + sg_out
+    L.rcn_sg_set_chunk_bytes.restype = C.c_int
+    L.rcn_sg_set_chunk_bytes.argtypes = [vp, i64]
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

@@ -154,6 +154,8 @@ struct rcn_ctx {
     DevBuf scale_dev;        // one ScaleDev: what the kernels read
     DevBuf desc_bad;         // desc.hip: keypoints outside their descriptor map since the last rcn_desc_sample_errors
     DevBuf kp_ws;            // keypoints.hip: candidate lists, heat map / status when the caller keeps neither, scale rows
+    DevBuf sg_ws, sg_scores; // superglue.hip: u, v, argmax rows, partial column sums; the scores of rcn_sg_match_device
+    int64_t sg_chunk_bytes = 0;   // bytes of score matrices per chunk of pairs (rcn_sg_set_chunk_bytes; <= 0: no limit)
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)
