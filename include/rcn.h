@@ -48,9 +48,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_match_stats; revision 2 -> 3 added rows_brute_force, chunks, coarse_launches to it and rcn_ba_factor_plan to the library;
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
  * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
- * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options).
+ * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options;
+ * 8 -> 9 the graph network rcn_sg_net_*).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 8
+#define RCN_ABI_REVISION 9
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -184,6 +185,61 @@ int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t stride_pair0,
                         int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
                         int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev);
 int rcn_sg_set_chunk_bytes(rcn_ctx *ctx, int64_t bytes);
+/* ---- SuperGlue's attentional graph network, weights supplied -------
+ * What matchFeatures runs in front of the layer above: normalizeFeatCoords (utils.cpp:119-149), the keypoint encoder, L self /
+ * cross attention layers and the final projection (Sarlin et al., CVPR 2020, section 3.1).  The library ships no weights: the
+ * caller hands over PLAIN linear layers (BatchNorm folded on the host: s = gamma / sqrt(var + 1e-5), W' = s W,
+ * b' = s (b - mean) + beta; reconstructor_amd/superglue_gnn.py does it in float64), fp32, in one packed block:
+ *   the encoder's five layers 3 -> 32 -> 64 -> 128 -> 256 -> 256, each W row-major [Cout][Cin] then b [Cout];
+ *   per layer: q, k, v, merge (each W [256][256], b [256]), mlp0 (W [512][512] over [x; msg], b [512]), mlp1 (W [256][512], b [256]);
+ *   the final projection W [256][256], b [256].
+ * That is 109376 + 657152 L + 65792 floats; any other n_params is RCN_ERR_ARG.  Channels are in the published order: channel
+ * c of q, k, v is head c % 4 at depth c / 4.  layer_types[l]: RCN_SG_LAYER_SELF or RCN_SG_LAYER_CROSS.  The block is copied;
+ * a net belongs to its ctx and is destroyed before it.
+ *
+ * For one pair with m keypoints in image 0 and n in image 1 (D = 256, 4 heads of 64 channels, ReLU behind every encoder layer
+ * but the last and behind mlp0):
+ *   coordinates  with image shapes (H, W): cx = W / 2, cy = H / 2 in INTEGER division, scale = max(H, W) * 0.7 in double,
+ *                k = (float)((x - c) / scale) in double -- the reference's rule; without shapes they are taken as they are;
+ *   encoder      x = desc + MLP_enc([kx; ky; score]);
+ *   layer l      src = x of the same image (self) or of the other (cross), both images from the values before the layer:
+ *                q = Wq x + bq, k = Wk src + bk, v = Wv src + bv; per head P = softmax_j(q_i . k_j / 8), o_i = sum_j P_ij v_j;
+ *                msg = Wm o + bm; x += W2 relu(W1 [x; msg] + b1) + b2;
+ *   output       mdesc = Wf x + bf: the descriptors rcn_sg_scores_device takes with D = 256; alpha is bin_score.
+ * Storage and arithmetic are fp32 (products on the fp32-input matrix instructions: fmaf chains in a fixed order); the tolerance
+ * against the float64 statement is derived in DESIGN section 21.  A pair's result is bit for bit the same alone, in any batch
+ * and under any chunking.
+ *
+ * kpts [B][M][2] (x, y) and scores [B][M] for image 0, [B][N][2] and [B][N] for image 1; descriptors by element strides (pair,
+ * row, d) as in rcn_sg_scores_device; shape0 / shape1: [B][2] int32 (H, W) in HBM, both or neither; m_dev / n_dev as above.
+ * mdesc0_out [B][M][256], mdesc1_out [B][N][256].  A pair with m == 0 or n == 0 computes nothing and its mdesc is not written;
+ * points past a pair's counts are never read and never written.  Non-finite inputs propagate (the status of the layer above
+ * reports them).  The activations (8 KiB per point) live in the ctx's workspace; pairs are processed in chunks under a fixed
+ * cap of that workspace, or rcn_sg_net_set_chunk_pairs pairs at a time (<= 0: the default); the result does not depend on it.
+ * RCN_ERR_ARG: null required pointer, a net of another ctx, B < 0, M < 1, N < 1, shapes for one side only, and for
+ * rcn_sg_net_create a layer count outside 0..1024, an unknown layer type, a wrong n_params, a non-finite bin_score.
+ * RCN_ERR_UNSUPPORTED: D != 256, M or N above RCN_SG_MAX_POINTS.  B == 0 launches nothing. */
+typedef struct rcn_sg_net rcn_sg_net;
+#define RCN_SG_LAYER_SELF  0
+#define RCN_SG_LAYER_CROSS 1
+int  rcn_sg_net_create(rcn_ctx *ctx, const int32_t *layer_types /*[n_layers]*/, int32_t n_layers, const float *params_host, int64_t n_params,
+                       double bin_score, rcn_sg_net **net_out);
+void rcn_sg_net_destroy(rcn_sg_net *net);
+int  rcn_sg_net_set_chunk_pairs(rcn_ctx *ctx, int32_t pairs);
+int  rcn_sg_net_forward_device(rcn_ctx *ctx, const rcn_sg_net *net, const float *kpts0_dev, const float *scores0_dev, const float *d0_dev,
+                               int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0, const float *kpts1_dev, const float *scores1_dev,
+                               const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                               const int32_t *shape0_dev /*[B][2] or NULL*/, const int32_t *shape1_dev, const int32_t *m_dev, const int32_t *n_dev,
+                               int32_t B, int32_t M, int32_t N, int32_t D, float *mdesc0_out_dev, float *mdesc1_out_dev);
+/* The forward into the ctx's workspace, then rcn_sg_match_device on it with alpha = bin_score (opt->alpha is ignored): bit for
+ * bit the two calls; outputs and their errors as there. */
+int  rcn_sg_net_match_device(rcn_ctx *ctx, const rcn_sg_net *net, const float *kpts0_dev, const float *scores0_dev, const float *d0_dev,
+                             int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0, const float *kpts1_dev, const float *scores1_dev,
+                             const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                             const int32_t *shape0_dev, const int32_t *shape1_dev, const int32_t *m_dev, const int32_t *n_dev,
+                             int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
+                             int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
+                             int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev);
 /* Host-side batch ingest: n_images images with their own row counts K[i] >= 0, each a dense row-major K[i] x D
  * fp32 matrix in HOST memory (rows[i]; what featDescToCV packs per call, FeatureMatcher.cpp:11-25 -- here for every
  * image of the loop at once), become ids first_img_id .. first_img_id + n_images - 1.  One device block of

@@ -39,6 +39,7 @@ SYMBOLS = [
     "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
     "rcn_kp_detect_device", "rcn_kp_nms_device",
     "rcn_sg_default_options", "rcn_sg_scores_device", "rcn_sg_assign_device", "rcn_sg_match_device", "rcn_sg_set_chunk_bytes",
+    "rcn_sg_net_create", "rcn_sg_net_destroy", "rcn_sg_net_set_chunk_pairs", "rcn_sg_net_forward_device", "rcn_sg_net_match_device",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -202,6 +203,17 @@ def load():
     L.rcn_sg_match_device.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, i32, i32, i32, i32, C.POINTER(SgOptions)] + sg_out
     L.rcn_sg_set_chunk_bytes.restype = C.c_int
     L.rcn_sg_set_chunk_bytes.argtypes = [vp, i64]
+    L.rcn_sg_net_create.restype = C.c_int
+    L.rcn_sg_net_create.argtypes = [vp, vp, i32, vp, i64, C.c_double, C.POINTER(vp)]
+    L.rcn_sg_net_destroy.restype = None
+    L.rcn_sg_net_destroy.argtypes = [vp]
+    L.rcn_sg_net_set_chunk_pairs.restype = C.c_int
+    L.rcn_sg_net_set_chunk_pairs.argtypes = [vp, i32]
+    sg_net_in = [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, i32]   # ctx, net, image 0, image 1, shapes, counts, B M N D
+    L.rcn_sg_net_forward_device.restype = C.c_int
+    L.rcn_sg_net_forward_device.argtypes = sg_net_in + [vp, vp]
+    L.rcn_sg_net_match_device.restype = C.c_int
+    L.rcn_sg_net_match_device.argtypes = sg_net_in + [C.POINTER(SgOptions)] + sg_out
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

@@ -156,6 +156,8 @@ struct rcn_ctx {
     DevBuf kp_ws;            // keypoints.hip: candidate lists, heat map / status when the caller keeps neither, scale rows
     DevBuf sg_ws, sg_scores; // superglue.hip: u, v, argmax rows, partial column sums; the scores of rcn_sg_match_device
     int64_t sg_chunk_bytes = 0;   // bytes of score matrices per chunk of pairs (rcn_sg_set_chunk_bytes; <= 0: no limit)
+    DevBuf gnn_ws, gnn_mdesc; // superglue_gnn.hip: the activations of one chunk of pairs; the matching descriptors of rcn_sg_net_match_device
+    int32_t gnn_chunk_pairs = 0;  // pairs per chunk of the graph network (rcn_sg_net_set_chunk_pairs; 0: as many as fit the default cap)
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)
@@ -334,6 +336,13 @@ void rcn_int_launch_cmp_fill(hipStream_t st, const int32_t *table_dev, int64_t s
 // fmat.hip: rcn_match_table_filter_device with ctx->mu already held
 int rcn_int_table_filter(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
                          int64_t stride, int32_t *counts_dev, int32_t *out_status_dev);
+// superglue.hip: rcn_sg_match_device with ctx->mu already held (rcn_sg_net_match_device, superglue_gnn.hip); check_only: the
+// argument checks alone, nothing launched and the descriptor pointers not looked at
+int rcn_int_sg_match(rcn_ctx *ctx, const char *who, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
+                     const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                     const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
+                     int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
+                     int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev, bool check_only);
 // match.hip internals shared with shard.hip (all expect ctx->mu held)
 int rcn_int_slab_attach(rcn_ctx *ctx, int32_t first_id, int32_t n_images, int32_t n_slots, const float *src,
                         int32_t K, int32_t D, int32_t conv_first, int32_t conv_n, int *slab_out,

@@ -615,15 +615,12 @@ extern "C" int rcn_sg_assign_device(rcn_ctx *ctx, const float *scores_dev, int64
     return sg_assign(ctx, who, scores_dev, stride_pair, stride_row, stride_col, m_dev, n_dev, B, M, N, o, out);
 }
 
-extern "C" int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
-                                   const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
-                                   const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
-                                   int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
-                                   int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev)
+int rcn_int_sg_match(rcn_ctx *ctx, const char *who, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
+                     const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                     const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
+                     int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
+                     int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev, bool check_only)
 {
-    if (!ctx) return RCN_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const char *who = "rcn_sg_match_device";
     rcn_sg_options o;
     rcn_sg_default_options(&o);
     if (opt) o = *opt;
@@ -632,6 +629,7 @@ extern "C" int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t st
     if (!sg_check_shape(ctx, who, B, M, N, &rc)) return rc;
     if (D < 1) { sg_fail(ctx, who, "D < 1"); return RCN_ERR_ARG; }
     if (!sg_check_options(ctx, who, o) || !sg_check_out(ctx, who, out, M)) return RCN_ERR_ARG;
+    if (check_only) return RCN_OK;
     if (!d0_dev || !d1_dev) { sg_fail(ctx, who, "null pointer"); return RCN_ERR_ARG; }
     if (B == 0) return RCN_OK;
     RCN_HIP(hipSetDevice(ctx->device));
@@ -639,4 +637,17 @@ extern "C" int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t st
     float *S = ctx->sg_scores.as<float>();
     if ((rc = sg_scores(ctx, d0_dev, stride_pair0, stride_row0, stride_d0, d1_dev, stride_pair1, stride_row1, stride_d1, m_dev, n_dev, B, M, N, D, S))) return rc;
     return sg_assign(ctx, who, S, (int64_t)M * N, N, 1, m_dev, n_dev, B, M, N, o, out);
+}
+
+extern "C" int rcn_sg_match_device(rcn_ctx *ctx, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
+                                   const float *d1_dev, int64_t stride_pair1, int64_t stride_row1, int64_t stride_d1,
+                                   const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
+                                   int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
+                                   int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return rcn_int_sg_match(ctx, "rcn_sg_match_device", d0_dev, stride_pair0, stride_row0, stride_d0, d1_dev, stride_pair1, stride_row1, stride_d1, m_dev, n_dev,
+                            B, M, N, D, opt, matches0_dev, matches1_dev, mscores0_dev, mscores1_dev, table_dev, table_stride, counts_dev, logP_out_dev,
+                            status_dev, false);
 }

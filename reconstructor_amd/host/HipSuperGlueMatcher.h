@@ -8,8 +8,13 @@
 //   matchFeaturesBatch B pairs in one call; the table (out[i] = feature of image 2 or -1) and the counts stay in HBM in the
 //                      layout of rcn_match_grid_device: rcn_match_compact_begin, rcn_match_table_filter_device and
 //                      everything behind them take them as they are
+// FeatureMatcherSuperglueNet is the whole of matchFeatures: the graph network in front (weights supplied
+// by the caller as the packed plain layers of rcn_sg_net_create) and the layer above behind it, through
+// rcn_sg_net_match_device, with the reference's own argument list; matchFeaturesBatch leaves the table in HBM.
 #pragma once
+#include <algorithm>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -125,6 +130,138 @@ private:
     int lastStatus_ = 0;
     int32_t *matches0_ = nullptr, *table_ = nullptr, *count_ = nullptr;
     float *scores0_ = nullptr;
+};
+
+// FeatureMatcherSuperglue (FeatureMatcherSuperglue.h) with the network on the GPU.  params / layerTypes / binScore: what
+// rcn_sg_net_create takes (reconstructor_amd/superglue_gnn.py folds a published state dict into them).
+class FeatureMatcherSuperglueNet {
+public:
+    FeatureMatcherSuperglueNet(const std::vector<int32_t> &layerTypes, const std::vector<float> &params, double binScore, rcn_ctx *ctx = nullptr,
+                               double matchThreshold = 0.2, double matchScoreThreshold = 0.5, int sinkhornIterations = 100)
+        : ctx_(ctx), owned_(false)
+    {
+        if (!ctx_) {
+            if (rcn_create(0, &ctx_) != RCN_OK) throw std::runtime_error("FeatureMatcherSuperglueNet: no usable gfx950 device");
+            owned_ = true;
+        }
+        rcn_sg_default_options(&opt_);
+        opt_.match_threshold = matchThreshold;
+        opt_.score_threshold = matchScoreThreshold;
+        opt_.iterations = sinkhornIterations;
+        if (rcn_sg_net_create(ctx_, layerTypes.data(), (int32_t)layerTypes.size(), params.data(), (int64_t)params.size(), binScore, &net_) != RCN_OK) {
+            const std::string why = rcn_last_error(ctx_);
+            if (owned_) rcn_destroy(ctx_);
+            throw std::runtime_error("FeatureMatcherSuperglueNet: " + why);
+        }
+    }
+    ~FeatureMatcherSuperglueNet()
+    {
+        release();
+        rcn_sg_net_destroy(net_);
+        if (owned_) rcn_destroy(ctx_);
+    }
+    FeatureMatcherSuperglueNet(const FeatureMatcherSuperglueNet &) = delete;
+    FeatureMatcherSuperglueNet &operator=(const FeatureMatcherSuperglueNet &) = delete;
+
+    // The reference's signature (FeatureMatcherSuperglue.cpp:51-55): the features carry a confidence (FeatureConf, as its
+    // featsToTensors assumes, :22) and a 256-float descriptor; imgShape = (height, width), normalised on the device by the
+    // reference's rule (utils.cpp:119-149).  matches[feature of image 1] = feature of image 2 above matchScoreThreshold (:82).
+    void matchFeatures(const std::vector<FeaturePtr<>> &features1, const std::vector<FeaturePtr<>> &features2, std::map<int, int> &matches,
+                       const std::pair<int, int> imgShape1, const std::pair<int, int> imgShape2)
+    {
+        const int m = (int)features1.size(), n = (int)features2.size();
+        if (m < 1 || n < 1) return;
+        const size_t pts = (size_t)m + n;
+        std::vector<float> host(pts * (2 + 1 + kDesc));
+        float *kp = host.data(), *sc = kp + 2 * pts, *de = sc + pts;
+        size_t at = 0;
+        for (const auto *feats : {&features1, &features2})
+            for (const auto &f : *feats) {
+                if (f->featDesc.desc.size() != (size_t)kDesc) throw std::runtime_error("matchFeatures: the network takes descriptors of 256 floats");
+                kp[2 * at] = (float)f->featCoord.x;
+                kp[2 * at + 1] = (float)f->featCoord.y;
+                sc[at] = (float)std::static_pointer_cast<FeatureConf<>>(f)->conf;
+                std::copy(f->featDesc.desc.begin(), f->featDesc.desc.end(), de + at * kDesc);
+                ++at;
+            }
+        const int32_t shapes[4] = {imgShape1.first, imgShape1.second, imgShape2.first, imgShape2.second};
+        reserve(pts, (size_t)m);
+        copyIn(in_, host.data(), host.size() * sizeof(float));
+        copyIn(shapes_, shapes, sizeof(shapes));
+        const float *dkp = in_, *dsc = dkp + 2 * pts, *dde = dsc + pts;
+        if (rcn_sg_net_match_device(ctx_, net_, dkp, dsc, dde, 0, kDesc, 1, dkp + 2 * (size_t)m, dsc + m, dde + (size_t)m * kDesc, 0, kDesc, 1, shapes_, shapes_ + 2,
+                                    nullptr, nullptr, 1, m, n, kDesc, &opt_, matches0_, nullptr, nullptr, nullptr, table_, m, count_, nullptr,
+                                    count_ + 1) != RCN_OK || rcn_synchronize(ctx_) != RCN_OK)
+            throw std::runtime_error(std::string("matchFeatures: ") + rcn_last_error(ctx_));
+        std::vector<int32_t> table((size_t)m);
+        int32_t cs[2] = {0, 0};
+        copyOut(table.data(), table_, table.size() * sizeof(int32_t));
+        copyOut(cs, count_, sizeof(cs));
+        lastStatus_ = cs[1];
+        int kept = 0;
+        for (int featIdx = 0; featIdx < m; ++featIdx)
+            if (table[featIdx] != -1) { matches[featIdx] = table[featIdx]; ++kept; }
+        if (kept != cs[0]) throw std::runtime_error("matchFeatures: the table and its count disagree");
+    }
+
+    // The batched form on device arrays: keypoints [pairs][maxFeatures][2] (x, y), confidences [pairs][maxFeatures], descriptors by
+    // (pair, feature, descriptor) element strides, image shapes [pairs][2] (height, width) or nullptr for coordinates that are
+    // normalised already, per-pair feature counts or nullptr.  tableDev [pairs][tableStride] and countsDev [pairs] stay in HBM.
+    void matchFeaturesBatch(const float *coords1Dev, const float *confs1Dev, const float *descs1Dev, int64_t strideP1, int64_t strideF1, int64_t strideD1,
+                            const float *coords2Dev, const float *confs2Dev, const float *descs2Dev, int64_t strideP2, int64_t strideF2, int64_t strideD2,
+                            const int32_t *imgShapes1Dev, const int32_t *imgShapes2Dev, const int32_t *featuresNum1Dev, const int32_t *featuresNum2Dev,
+                            int pairs, int maxFeatures1, int maxFeatures2, int32_t *tableDev, int64_t tableStride, int32_t *countsDev,
+                            int32_t *statusDev = nullptr)
+    {
+        if (pairs < 1) return;
+        reserve(0, (size_t)pairs * maxFeatures1);
+        if (rcn_sg_net_match_device(ctx_, net_, coords1Dev, confs1Dev, descs1Dev, strideP1, strideF1, strideD1, coords2Dev, confs2Dev, descs2Dev, strideP2,
+                                    strideF2, strideD2, imgShapes1Dev, imgShapes2Dev, featuresNum1Dev, featuresNum2Dev, pairs, maxFeatures1, maxFeatures2,
+                                    kDesc, &opt_, matches0_, nullptr, nullptr, nullptr, tableDev, tableStride, countsDev, nullptr, statusDev) != RCN_OK)
+            throw std::runtime_error(std::string("matchFeaturesBatch: ") + rcn_last_error(ctx_));
+    }
+    int lastStatus() const { return lastStatus_; }      // 1: the last pair of matchFeatures produced a non-finite score (no matches)
+    rcn_ctx *ctx() const { return ctx_; }
+    rcn_sg_options &options() { return opt_; }
+
+private:
+    static constexpr int kDesc = 256;
+    static constexpr int kMemcpyHostToDevice = 1, kMemcpyDeviceToHost = 2;   // hipMemcpyKind
+    void release()
+    {
+        for (void *p : {(void *)in_, (void *)shapes_, (void *)matches0_, (void *)table_, (void *)count_}) if (p) (void)hipFree(p);
+        in_ = nullptr; shapes_ = nullptr; matches0_ = nullptr; table_ = nullptr; count_ = nullptr;
+        capPts_ = capRows_ = 0;
+    }
+    void reserve(size_t pts, size_t rows)
+    {
+        if (pts <= capPts_ && rows <= capRows_ && count_) return;
+        pts = std::max(pts, capPts_);
+        rows = std::max(rows, capRows_);
+        release();
+        if (hipMalloc((void **)&in_, std::max<size_t>(1, pts) * (2 + 1 + kDesc) * sizeof(float)) || hipMalloc((void **)&shapes_, 4 * sizeof(int32_t)) ||
+            hipMalloc((void **)&matches0_, std::max<size_t>(1, rows) * sizeof(int32_t)) || hipMalloc((void **)&table_, std::max<size_t>(1, rows) * sizeof(int32_t)) ||
+            hipMalloc((void **)&count_, 2 * sizeof(int32_t)))
+            throw std::runtime_error("FeatureMatcherSuperglueNet: out of device memory");
+        capPts_ = pts; capRows_ = rows;
+    }
+    void copyIn(void *dst, const void *src, size_t bytes)
+    {
+        if (bytes && hipMemcpy(dst, src, bytes, kMemcpyHostToDevice)) throw std::runtime_error("FeatureMatcherSuperglueNet: host to device copy failed");
+    }
+    void copyOut(void *dst, const void *src, size_t bytes)
+    {
+        if (bytes && hipMemcpy(dst, src, bytes, kMemcpyDeviceToHost)) throw std::runtime_error("FeatureMatcherSuperglueNet: device to host copy failed");
+    }
+
+    rcn_ctx *ctx_;
+    bool owned_;
+    rcn_sg_net *net_ = nullptr;
+    rcn_sg_options opt_;
+    size_t capPts_ = 0, capRows_ = 0;
+    int lastStatus_ = 0;
+    float *in_ = nullptr;
+    int32_t *shapes_ = nullptr, *matches0_ = nullptr, *table_ = nullptr, *count_ = nullptr;
 };
 
 }  // namespace reconstructor::Core
