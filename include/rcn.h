@@ -49,9 +49,9 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
  * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
  * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options;
- * 8 -> 9 the graph network rcn_sg_net_*).
+ * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 9
+#define RCN_ABI_REVISION 10
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -240,6 +240,51 @@ int  rcn_sg_net_match_device(rcn_ctx *ctx, const rcn_sg_net *net, const float *k
                              int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
                              int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
                              int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev);
+/* ---- SuperPoint's convolutional network, weights supplied -----------
+ * The forward pass of FeatureSuperPoint::detect (FeatureSuperPoint.cpp:228-263, superNet.forward): image in, the two outputs
+ * the keypoint and descriptor stages above take.  DeTone et al., CVPR-W 2018.  The library ships no weights: the caller hands
+ * over one packed fp32 block of RCN_SP_N_PARAMS floats in the order
+ *   conv1a 1->64, conv1b 64->64, conv2a 64->64, conv2b 64->64, conv3a 64->128, conv3b 128->128, conv4a 128->128, conv4b 128->128,
+ *   convPa 128->256, convPb 256->65 (1 x 1), convDa 128->256, convDb 256->256 (1 x 1),
+ * each layer W row-major [Cout][Cin][3][3] ([Cout][Cin] for 1 x 1), then b [Cout].  The block is copied (and laid out anew for
+ * the kernels); a net belongs to its ctx and is destroyed before it.
+ *
+ * For one grey image [H][W] in [0, 1], H and W positive multiples of 8, Hc = H / 8, Wc = W / 8:
+ *   encoder     conv1a, conv1b, pool, conv2a, conv2b, pool, conv3a, conv3b, pool, conv4a, conv4b; every convolution 3 x 3,
+ *               stride 1, zero padding 1, plus bias, then ReLU; pool is 2 x 2 max, stride 2;
+ *   detector    logits = convPb(relu(convPa(x))), [Hc][Wc][65];
+ *   descriptor  d = convDb(relu(convDa(x))), [Hc][Wc][256]; with RCN_SP_NORMALIZE_DESC every cell is divided by its L2 norm:
+ *               the fp32 sum of the squares in ascending channel order, sqrtf, fp32 division (a zero cell gives NaN).
+ * Storage and arithmetic are fp32 (products on the fp32-input matrix instructions: fmaf chains in a fixed order); the tolerance
+ * against the float64 statement is derived in DESIGN section 22.  An image's result is bit for bit the same alone, in any
+ * batch, under any chunking and from any strides.
+ *
+ * images_dev: n images addressed by ELEMENT strides (image, y, x); RCN_SP_INPUT_F32: float; RCN_SP_INPUT_U8: bytes, a pixel
+ * is (float)((double)v / 255.0), prepImg's rule (:278-285).  Both outputs are channel-last and dense: what
+ * rcn_kp_detect_device reads with strides (Hc Wc 65, 1, Wc 65, 65) and rcn_desc_sample_batch_device with (Hc Wc 256, 1,
+ * Wc 256, 256).  The activations (320 bytes per pixel) live in the ctx's workspace; images are processed in chunks under a
+ * fixed cap of that workspace (one image always fits: the workspace grows), or rcn_sp_net_set_chunk_images images at a time
+ * (<= 0: the default).  Non-finite inputs propagate.
+ * RCN_ERR_ARG: null required pointer, a net of another ctx, n < 0, H or W no positive multiple of 8, H * W > 2^31 - 1, an
+ * unknown dtype or flag bit, a wrong n_params.  n == 0 launches nothing. */
+typedef struct rcn_sp_net rcn_sp_net;
+#define RCN_SP_N_PARAMS 1300865
+#define RCN_SP_NORMALIZE_DESC 1          /* flags */
+#define RCN_SP_INPUT_F32 0
+#define RCN_SP_INPUT_U8  1
+int  rcn_sp_net_create(rcn_ctx *ctx, const float *params_host, int64_t n_params, rcn_sp_net **net_out);
+void rcn_sp_net_destroy(rcn_sp_net *net);
+int  rcn_sp_net_set_chunk_images(rcn_ctx *ctx, int32_t images);
+int  rcn_sp_net_forward_device(rcn_ctx *ctx, const rcn_sp_net *net, const void *images_dev, int32_t input_dtype,
+                               int64_t stride_img, int64_t stride_y, int64_t stride_x, int32_t n, int32_t H, int32_t W, int32_t flags,
+                               float *logits_out_dev /*[n][Hc][Wc][65]*/, float *desc_out_dev /*[n][Hc][Wc][256]*/);
+/* The forward into the ctx's workspace, then rcn_kp_detect_device and rcn_desc_sample_batch_device on it: bit for bit the
+ * three calls.  Keypoint arguments, outputs and their errors as there; rows_out_dev [n][K][D]. */
+int  rcn_sp_net_detect_device(rcn_ctx *ctx, const rcn_sp_net *net, const void *images_dev, int32_t input_dtype,
+                              int64_t stride_img, int64_t stride_y, int64_t stride_x, int32_t n, int32_t H, int32_t W, int32_t flags,
+                              int32_t heat_mode, double conf_thresh, int32_t nms_radius, int32_t border, int32_t K, int32_t D,
+                              int32_t *kp_xy_dev, float *conf_dev, int32_t *counts_dev, float *rows_out_dev /*[n][K][D]*/,
+                              float *heat_out_dev /*may be NULL*/, int32_t *rounds_dev /*may be NULL*/);
 /* Host-side batch ingest: n_images images with their own row counts K[i] >= 0, each a dense row-major K[i] x D
  * fp32 matrix in HOST memory (rows[i]; what featDescToCV packs per call, FeatureMatcher.cpp:11-25 -- here for every
  * image of the loop at once), become ids first_img_id .. first_img_id + n_images - 1.  One device block of

@@ -40,6 +40,7 @@ SYMBOLS = [
     "rcn_kp_detect_device", "rcn_kp_nms_device",
     "rcn_sg_default_options", "rcn_sg_scores_device", "rcn_sg_assign_device", "rcn_sg_match_device", "rcn_sg_set_chunk_bytes",
     "rcn_sg_net_create", "rcn_sg_net_destroy", "rcn_sg_net_set_chunk_pairs", "rcn_sg_net_forward_device", "rcn_sg_net_match_device",
+    "rcn_sp_net_create", "rcn_sp_net_destroy", "rcn_sp_net_set_chunk_images", "rcn_sp_net_forward_device", "rcn_sp_net_detect_device",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -214,6 +215,17 @@ def load():
     L.rcn_sg_net_forward_device.argtypes = sg_net_in + [vp, vp]
     L.rcn_sg_net_match_device.restype = C.c_int
     L.rcn_sg_net_match_device.argtypes = sg_net_in + [C.POINTER(SgOptions)] + sg_out
+    L.rcn_sp_net_create.restype = C.c_int
+    L.rcn_sp_net_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
+    L.rcn_sp_net_destroy.restype = None
+    L.rcn_sp_net_destroy.argtypes = [vp]
+    L.rcn_sp_net_set_chunk_images.restype = C.c_int
+    L.rcn_sp_net_set_chunk_images.argtypes = [vp, i32]
+    sp_net_in = [vp, vp, vp, i32, i64, i64, i64, i32, i32, i32, i32]   # ctx, net, images, dtype, strides, n H W, flags
+    L.rcn_sp_net_forward_device.restype = C.c_int
+    L.rcn_sp_net_forward_device.argtypes = sp_net_in + [vp, vp]
+    L.rcn_sp_net_detect_device.restype = C.c_int
+    L.rcn_sp_net_detect_device.argtypes = sp_net_in + [i32, C.c_double, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

@@ -108,12 +108,19 @@ extern "C" int rcn_desc_sample_batch_device(rcn_ctx *ctx, const float *desc_maps
 {
     if (!ctx) return RCN_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
+    return rcn_int_desc_sample_batch(ctx, desc_maps_dev, stride_img, stride_c, stride_y, stride_x, Hc, Wc, kp_xy_dev, counts_dev, n, K, D, out_rows_dev, false);
+}
+
+int rcn_int_desc_sample_batch(rcn_ctx *ctx, const float *desc_maps_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y,
+                              int64_t stride_x, int32_t Hc, int32_t Wc, const int32_t *kp_xy_dev, const int32_t *counts_dev,
+                              int32_t n, int32_t K, int32_t D, float *out_rows_dev, bool check_only)
+{
     if (n < 0 || n > 65535 || K < 0 || D < 1 || D > 256 || Hc < 1 || Wc < 1 ||
         (n > 0 && K > 0 && (!desc_maps_dev || !kp_xy_dev || !counts_dev || !out_rows_dev))) {
         ctx->set_error("rcn_desc_sample_batch_device: bad argument (1 <= D <= 256, n <= 65535)");
         return RCN_ERR_ARG;
     }
-    if (n == 0 || K == 0) return RCN_OK;
+    if (n == 0 || K == 0 || check_only) return RCN_OK;
     RCN_HIP(hipSetDevice(ctx->device));
     if (!ctx->desc_bad.p) {
         RCN_HIP(ctx->desc_bad.reserve(sizeof(unsigned)));

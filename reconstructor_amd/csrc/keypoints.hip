@@ -405,12 +405,20 @@ extern "C" int rcn_kp_detect_device(rcn_ctx *ctx, const float *logits_dev, int64
 {
     if (!ctx) return RCN_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
+    return rcn_int_kp_detect(ctx, logits_dev, stride_img, stride_c, stride_y, stride_x, n, H, W, heat_mode, conf_thresh, nms_radius, border, K,
+                             kp_xy_dev, conf_dev, counts_dev, heat_out_dev, rounds_dev, false);
+}
+
+int rcn_int_kp_detect(rcn_ctx *ctx, const float *logits_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                      int32_t n, int32_t H, int32_t W, int32_t heat_mode, double conf_thresh, int32_t nms_radius, int32_t border,
+                      int32_t K, int32_t *kp_xy_dev, float *conf_dev, int32_t *counts_dev, float *heat_out_dev, int32_t *rounds_dev, bool check_only)
+{
     if (!kp_check(ctx, "rcn_kp_detect_device", true, logits_dev, n, H, W, nms_radius, border, K, kp_xy_dev, counts_dev)) return RCN_ERR_ARG;
     if (heat_mode != RCN_KP_HEAT_REFERENCE && heat_mode != RCN_KP_HEAT_SOFTMAX) {
         ctx->set_error("rcn_kp_detect_device: bad argument (unknown heat mode)");
         return RCN_ERR_ARG;
     }
-    if (n == 0) return RCN_OK;
+    if (n == 0 || check_only) return RCN_OK;
     RCN_HIP(hipSetDevice(ctx->device));
     if (int rc = kp_nms_setup(ctx)) return rc;
     const bool ref = heat_mode == RCN_KP_HEAT_REFERENCE;

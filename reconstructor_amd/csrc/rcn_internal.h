@@ -158,6 +158,8 @@ struct rcn_ctx {
     int64_t sg_chunk_bytes = 0;   // bytes of score matrices per chunk of pairs (rcn_sg_set_chunk_bytes; <= 0: no limit)
     DevBuf gnn_ws, gnn_mdesc; // superglue_gnn.hip: the activations of one chunk of pairs; the matching descriptors of rcn_sg_net_match_device
     int32_t gnn_chunk_pairs = 0;  // pairs per chunk of the graph network (rcn_sg_net_set_chunk_pairs; 0: as many as fit the default cap)
+    DevBuf sp_ws, sp_out;     // superpoint_net.hip: the activations of one chunk of images; the logits and descriptor maps of rcn_sp_net_detect_device
+    int32_t sp_chunk_images = 0;  // images per chunk of SuperPoint's network (rcn_sp_net_set_chunk_images; 0: as many as fit the default cap)
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)
@@ -343,6 +345,14 @@ int rcn_int_sg_match(rcn_ctx *ctx, const char *who, const float *d0_dev, int64_t
                      const int32_t *m_dev, const int32_t *n_dev, int32_t B, int32_t M, int32_t N, int32_t D, const rcn_sg_options *opt,
                      int32_t *matches0_dev, int32_t *matches1_dev, float *mscores0_dev, float *mscores1_dev,
                      int32_t *table_dev, int64_t table_stride, int32_t *counts_dev, float *logP_out_dev, int32_t *status_dev, bool check_only);
+// keypoints.hip / desc.hip: rcn_kp_detect_device and rcn_desc_sample_batch_device with ctx->mu already held
+// (rcn_sp_net_detect_device, superpoint_net.hip); check_only: the argument checks alone, nothing launched
+int rcn_int_kp_detect(rcn_ctx *ctx, const float *logits_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                      int32_t n, int32_t H, int32_t W, int32_t heat_mode, double conf_thresh, int32_t nms_radius, int32_t border,
+                      int32_t K, int32_t *kp_xy_dev, float *conf_dev, int32_t *counts_dev, float *heat_out_dev, int32_t *rounds_dev, bool check_only);
+int rcn_int_desc_sample_batch(rcn_ctx *ctx, const float *desc_maps_dev, int64_t stride_img, int64_t stride_c, int64_t stride_y,
+                              int64_t stride_x, int32_t Hc, int32_t Wc, const int32_t *kp_xy_dev, const int32_t *counts_dev,
+                              int32_t n, int32_t K, int32_t D, float *out_rows_dev, bool check_only);
 // match.hip internals shared with shard.hip (all expect ctx->mu held)
 int rcn_int_slab_attach(rcn_ctx *ctx, int32_t first_id, int32_t n_images, int32_t n_slots, const float *src,
                         int32_t K, int32_t D, int32_t conv_first, int32_t conv_n, int *slab_out,
