@@ -1,6 +1,6 @@
-// chol_plan.h -- the schedule of the dense blocked Cholesky (K7, ba.hip) as DATA: a list of tile operations in an order that is a
+// chol_plan.h -- the schedule of the dense blocked Cholesky (K7, chol.hip) as DATA: a list of tile operations in an order that is a
 // correct SEQUENTIAL algorithm, each with the stream it runs on and the device counters it has to wait for.  Pure host code (no HIP):
-// ba.hip launches the list, tests/test_chol_plan.py executes it in numpy -- in list order and in random orders that respect only the
+// chol.hip launches the list, tests/test_chol_plan.py executes it in numpy -- in list order and in random orders that respect only the
 // waits -- and checks that no two operations the waits leave unordered touch a common tile (one of them writing).
 //
 // The cross-stream waits are not written by hand: every operation declares the tiles it reads and writes (S = the system and its
@@ -21,6 +21,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace chol {
@@ -75,6 +76,15 @@ struct Params {
                           // left, and that measures the same either way (8.42-8.51 against 8.36-8.48 ms): the shipping plan keeps to three streams -- a process's
                           // sixth stream is a slow one on this pool (EXPERIMENTS.md), and the library should not be the one that uses the fifth up
 };
+static_assert(sizeof(Params) == 14 * sizeof(int), "Params is ints only: operator== compares the bytes");
+inline bool operator==(const Params &a, const Params &b) { return std::memcmp(&a, &b, sizeof(Params)) == 0; }
+// The array form of rcn_ba_factor_plan (include/rcn.h): thirteen values in a fixed order; nblk is the caller's.
+inline Params params_from_array(const int32_t *v)
+{
+    Params p;
+    p.tl_g = v[0]; p.tl_min = v[1]; p.pair = v[2]; p.pair_min = v[3]; p.pipe_min = v[4]; p.pg_stream = v[5]; p.fuse_tail = v[6]; p.head_small = v[7]; p.tl_serial = v[8]; p.window = v[9]; p.diag_server = v[10]; p.bulk_behind = v[11]; p.carve_rows = v[12];
+    return p;
+}
 
 struct Plan {
     Params prm;

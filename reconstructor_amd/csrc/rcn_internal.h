@@ -11,7 +11,6 @@
 #include <vector>
 
 #include "../../include/rcn.h"
-#include "chol_plan.h"
 
 #define RCN_HIP(call)                                                                    \
     do {                                                                                 \
@@ -38,6 +37,7 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+#include "chol.h"      // CholState holds DevBufs
 
 // Per-image device record (mirrored in a device table for the kernels).
 struct ImgDev {
@@ -241,40 +241,10 @@ struct rcn_ctx {
     uint64_t ba_graph_serial = 0;
     uint64_t ba_pair_token = 0;         // whose pair lists the Schur-build workspace holds (0 = nobody's)
     std::vector<int> ba_pair_camdim;    // ... and the per-camera tangent dimensions they were built for (a camera without free parameters has no pairs)
-    hipStream_t aux_stream = nullptr;   // lookahead stream of the Cholesky: bulk trailing updates (CU mask leaves one CU per XCD to the diagonal kernel)
-    hipStream_t chain_stream = nullptr;  // diagnostic build (RCN_CHOL_CHAIN_STREAM=1): the factorisation's chain on a highest-priority stream of the library's own
-    int chol_chain_stream = 0;
-    hipStream_t diag_stream = nullptr;   // the resident workgroup that factors the diagonal blocks of a factorisation (k_chol_diag_server)
-    hipStream_t panel2_stream = nullptr; // two-level regime of the Cholesky, plans with pg_stream only (not what ships): the panel product for the rows below the head (same CU mask); made on demand
-    std::vector<uint32_t> bulk_cu_mask;  // the bulk stream's CU mask
-    hipStream_t panel_stream = nullptr; // second chain stream of the Cholesky: panels and first trailing columns behind the critical tile (same CU mask)
-    // the factorisation's schedule (chol_plan.h: operations, streams, waits, tile maps) for the last shape solved; its maps in HBM
-    DevBuf bulk_map;
-    chol::Plan chol_plan;
-    DevBuf diag_items;                               // the resident diagonal workgroup's work list of that plan
-    bool chol_plan_valid = false;
-    int chol_tl_g = 4;                               // two-level regime: panels per super-step (K = 128 g per bulk update); 0 = right-looking steps only (diagnostic build: RCN_CHOL_TL)
-    int chol_diag_server = 0;                        // diagnostic build (RCN_CHOL_DIAG_SERVER=1): the diagonal blocks in one resident workgroup instead of a launch per block on the chain's stream
-    int chol_bulk_behind = 0;                        // right-looking regime: a bulk update starts when the next diagonal block's kernel has started (chol_plan.h; RCN_CHOL_BULK_BEHIND=1 in the diagnostic build: measured, not shipped)
-    int chol_carve_rows = 0;                         // right-looking regime: the chain's next tiles as latency-kernel operations of their own from this many rows on (chol_plan.h; RCN_CHOL_CARVE)
-    int chol_window = 0;                             // two-level regime: 2 g-row window of the chain's latency kernels (RCN_CHOL_WINDOW)
-    int chol_tl_serial = 0;                          // two-level regime: super-blocks with fewer tile rows below them run their small operations on the chain's stream (RCN_CHOL_TL_SERIAL)
-    int chol_head_small = 1;                         // two-level regime: head rows' product + next super-diagonal block's update through k_gemm_qm (RCN_CHOL_HEAD_SMALL)
-    int chol_fuse_tail = 1;                          // two-level regime: the panel product below the head rows as the tail of the previous bulk launch (RCN_CHOL_FUSE_TAIL)
-    int chol_pg_stream = 0;                          // two-level regime: the panel product below the head rows on a stream of its own (RCN_CHOL_PGSTREAM)
-    bool chol_pg_prio = true;                        // diagnostic build (RCN_CHOL_PG_PRIO=0): no raised wave priority for the panel product below the head rows
-    int chol_gate_in_kernel = 0;                     // diagnostic build (RCN_CHOL_GATE_IN_KERNEL=1): waits of the small kernels off the chain inside them, not in a gate kernel in front; -1: in front on the chain too
-    bool chol_host_time = false;                     // diagnostic build (RCN_CHOL_HOSTTIME=1): print the host time of every factorisation's enqueue
-    int chol_tl_min = 40;                            // ... while at least this many tile rows remain below the super-block (RCN_CHOL_TL_MIN)
-    int chol_group = 2;                              // right-looking regime: panels per bulk update while many tile rows remain, 2 (K = 256) or 1
-    int chol_pipe_min = 32;                          // panel / column kernels go through the pipelined kernel from this many tiles on
-    bool trsv_chain = true;                          // backward substitution as one launch (k_trsv_bwd_chain); off after a flag timeout
-    int chol_break = 0;                              // diagnostic build: 1 = break one cross-stream hand-off (forces the one-stream fallback); 2 = and put a NaN pivot behind it
-    int chol_pair_min = 24;                          // two-panel bulk updates while at least this many tile rows remain below the pair
-    bool chol_safe = false;             // a device-counter hand-off timed out once: factorise on one stream, in plain order, from then on
+    CholState chol;                     // the dense factorisation of the reduced system (chol.h, chol.hip)
     double *ba_host_scal = nullptr;   // pinned mirror of the LM step's scalars (16 doubles; [15]: sequence number), written by the step's last kernel
     unsigned long long ba_host_seq = 0;
-    hipEvent_t ba_ev[9];             // [0]: fork of the factorisation's streams, [1..4]: their joins, [5]: the chain's own stream back to the caller's, [7]: pair lists
+    hipEvent_t ba_pair_ev;           // the pair lists of the Schur build are there
     hipEvent_t ba_tev[6];            // phase timing of rcn_ba_solve ([4], [5]: around k_ba_eval<true>)
     bool ba_ev_made = false;
 

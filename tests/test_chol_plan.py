@@ -374,6 +374,35 @@ def test_the_shipping_schedule_at_cfg5_is_two_level():
             assert cnt[i, j] == want, (i, j, cnt[i, j], want)
 
 
+def raw_plan(nblk, params):
+    """the operation words and the maps exactly as rcn_ba_factor_plan writes them"""
+    lib = _lib.load()
+    fn = lib.rcn_ba_factor_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    prm = None if params is None else np.asarray(params, dtype=np.int32)
+    pp = None if prm is None else prm.ctypes.data
+    n_ops, n_maps = C.c_int64(0), C.c_int64(0)
+    fn(nblk, pp, None, 0, None, 0, C.byref(n_ops), C.byref(n_maps))
+    ops = np.zeros((max(n_ops.value, 1), OPW), dtype=np.int32)
+    maps = np.zeros(max(n_maps.value, 1), dtype=np.uint32)
+    assert fn(nblk, pp, ops.ctypes.data, n_ops.value, maps.ctypes.data, n_maps.value, C.byref(n_ops), C.byref(n_maps)) == 0
+    return ops[:n_ops.value], maps[:n_maps.value]
+
+
+@pytest.mark.parametrize("nblk", [3, 44, 79])      # 3: the smallest plan with more than one stream; 44: the smallest with a two-level super-step (nblk - 4 >= 40); 79: cfg 5
+def test_default_parameters_are_the_shipping_ones(nblk):
+    """params == NULL means the defaults of chol::Params, the only place they are written down: the same operations and maps as the
+    thirteen shipping values given explicitly."""
+    ops_d, maps_d = raw_plan(nblk, None)
+    ops_e, maps_e = raw_plan(nblk, (4, 40, 1, 24, 32, 0, 1, 1, 0, 0, 0, 0, 0))
+    assert len(ops_d) > 0
+    assert np.array_equal(ops_d, ops_e) and np.array_equal(maps_d, maps_e)
+    assert len(set(ops_d[:, 1].tolist())) > 1
+    if nblk >= 44:
+        assert (ops_d[:, 0] == SINV).any()
+
+
 def test_bulk_updates_behind_the_next_diagonal_block():
     """The plan option bulk_behind (measured, not shipped): a bulk update of the right-looking regime is listed behind the next diagonal
     block and waits for the chain's counter to say that block's kernel has started (the value the block publishes with its first thread)."""

@@ -1,6 +1,6 @@
 // tools/chol_diag_bench.hip -- diagnostic: phase timing of k_chol_diag on one 128x128 SPD block.
 #define RCN_STAMP 1
-#include "../reconstructor_amd/csrc/ba.hip"
+#include "../reconstructor_amd/csrc/chol.hip"
 #include <cstdio>
 #include <vector>
 int main()

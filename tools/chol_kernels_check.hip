@@ -4,7 +4,7 @@
 //   * k_gemm_qm<1>, <2>        the latency form of both for the handful of head tiles
 //   * k_sinv                   block rows of a super-block's inverse, g = 4 and g = 8:  W L_JJ = I
 // Prints one line per check and "ALL OK" at the end; exit code 1 on the first failure.
-#include "../reconstructor_amd/csrc/ba.hip"
+#include "../reconstructor_amd/csrc/chol.hip"
 #include <cstdio>
 #include <vector>
 

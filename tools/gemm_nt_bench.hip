@@ -1,5 +1,5 @@
 // tools/gemm_nt_bench.hip -- diagnostic: the bulk trailing-update kernel on a synthetic 10112^2 system (panels from column block 0).
-#include "../reconstructor_amd/csrc/ba.hip"
+#include "../reconstructor_amd/csrc/chol.hip"
 #include <cstdio>
 #include <vector>
 int main()
