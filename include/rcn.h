@@ -920,6 +920,73 @@ void rcn_store_close(rcn_store *store);
 /* descriptors (and coordinates) of every stored image into the ctx: rcn_desc_upload / rcn_coords_upload per image */
 int  rcn_store_upload(rcn_ctx *ctx, const rcn_store *store);
 
+/* ---- SIFT: FeatureClassic::detect (FeatureDetector.cpp:13-35 = cv::SIFT::create()->detectAndCompute) --------------
+ * Lowe's detector and descriptor with cv::SIFT::create()'s defaults, restated in tests/sift_ref.py (DESIGN section 23;
+ * what could not be pinned against OpenCV itself is listed in section 1).  Fixed: first octave -1 (the image is doubled),
+ * border 5, at most 5 interpolation steps, 36 orientation bins, descriptor 4 x 4 x 8, integer factor 512.
+ *
+ * The Gaussian pyramid is fp32 (separable blurs through LDS, weights computed in double on the host and rounded once,
+ * reflect-101 border, taps summed in ascending order); everything behind it reads the fp32 pyramid and computes in fp64.
+ * An image's result does not depend on the batch, the chunking, the strides or the input type of equal values.
+ *
+ * Packed pyramid of one image: octave o has S + 3 layers of oct_h[o] x oct_w[o] floats, layer i of octave o starts at
+ * element layer_offset[o][i]; floats_per_image in all.  rcn_sift_layout is pure host code (no device needed). */
+#define RCN_SIFT_MAX_OCTAVES 16
+#define RCN_SIFT_MAX_LAYERS  8           /* S + 3 */
+#define RCN_SIFT_MAX_TAPS    96
+#define RCN_SIFT_INPUT_F32 0             /* pixels on the 0..255 scale */
+#define RCN_SIFT_INPUT_U8  1
+typedef struct {
+    int32_t n_octave_layers;             /* S: 3, supported 1..5 */
+    int32_t reserved;
+    double  contrast_threshold;          /* 0.04, >= 0 */
+    double  edge_threshold;              /* 10, > 0 */
+    double  sigma;                       /* 1.6; > 0 and small enough that no blur needs more than RCN_SIFT_MAX_TAPS taps */
+} rcn_sift_options;
+typedef struct {
+    int32_t n_octaves, n_layers;         /* nOct, S + 3 */
+    int32_t base_taps, reserved;
+    double  base_sigma;                  /* sqrt(max(sigma^2 - 1, 0.01)): the blur of the doubled image */
+    int32_t oct_h[RCN_SIFT_MAX_OCTAVES], oct_w[RCN_SIFT_MAX_OCTAVES];
+    double  layer_sigma[RCN_SIFT_MAX_LAYERS];   /* [0] = sigma; [i] the blur that makes layer i from layer i - 1 */
+    int32_t layer_taps[RCN_SIFT_MAX_LAYERS];    /* [0] = 0 */
+    int64_t layer_offset[RCN_SIFT_MAX_OCTAVES][RCN_SIFT_MAX_LAYERS];
+    int64_t floats_per_image;
+} rcn_sift_pyramid_layout;
+void rcn_sift_default_options(rcn_sift_options *opt);
+/* opt == NULL: the defaults.  RCN_ERR_ARG: min(H, W) < 16, 4 H W > 2^31 - 1, an option out of range. */
+int  rcn_sift_layout(int32_t H, int32_t W, const rcn_sift_options *opt, rcn_sift_pyramid_layout *out);
+/* images per pass over the ctx's workspace (<= 0: as many as fit its default cap of 1 GiB) */
+int  rcn_sift_set_chunk_images(rcn_ctx *ctx, int32_t images);
+/* images_dev: n grey images [H][W] addressed by ELEMENT strides (image, y, x), as rcn_sp_net_forward_device reads them.
+ * pyr_out_dev: [n][floats_per_image].  Asynchronous on the ctx stream. */
+int  rcn_sift_pyramid_device(rcn_ctx *ctx, const void *images_dev, int32_t input_dtype, int64_t stride_img, int64_t stride_y,
+                             int64_t stride_x, int32_t n, int32_t H, int32_t W, const rcn_sift_options *opt, float *pyr_out_dev);
+/* The extrema alone, for inspection: a pixel of DoG layer 1..S, at least 5 from the border, with |v| > floor(0.5 contrast / S * 255) that
+ * is >= (v > 0) or <= (v < 0) all 26 neighbours -- fp32 comparisons only, so the set is exact given the pyramid.  A record is
+ * (octave << 56) | (layer << 52) | (row << 26) | column, in no particular order; counts[i] is the number found, of which the first
+ * `capacity` were stored. */
+int  rcn_sift_candidates_device(rcn_ctx *ctx, const float *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_sift_options *opt,
+                                int32_t capacity, uint64_t *cand_out_dev /*[n][capacity]*/, int32_t *counts_dev /*[n]*/);
+/* The stages behind the pyramid (extrema, refinement, orientation, duplicates, order, cap) on pyramids the caller has.
+ * Keypoints in ascending order of (x, y, size, angle, response, packed octave); counts[i] is the uncapped number -- when it
+ * exceeds K the K largest by (response descending, canonical rank ascending) are emitted, still in canonical order.  Rows
+ * past min(counts[i], K): xy and xy_int (-1, -1), the other fields 0.  xy_int is xy truncated toward zero (Feature<int>::featCoord).
+ * counts[i] = -1 (and no rows): the image had more extrema than the workspace holds (one per 8 pyramid pixels and layer, above the 2 / 27 of uncorrelated noise). */
+int  rcn_sift_detect_device(rcn_ctx *ctx, const float *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_sift_options *opt, int32_t K,
+                            float *xy_dev /*[n][K][2]*/, int32_t *xy_int_dev /*[n][K][2]*/, float *size_dev /*[n][K]*/,
+                            float *angle_dev /*[n][K]*/, float *response_dev /*[n][K]*/, int32_t *octave_dev /*[n][K]*/,
+                            int32_t *counts_dev /*[n]*/);
+/* 128 integer-valued floats per keypoint, rows past min(counts[i], K) zero (the local_K contract of rcn_shard_exchange) */
+int  rcn_sift_describe_device(rcn_ctx *ctx, const float *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_sift_options *opt, int32_t K,
+                              const float *xy_dev, const float *size_dev, const float *angle_dev, const int32_t *octave_dev,
+                              const int32_t *counts_dev, float *rows_out_dev /*[n][K][128]*/);
+/* The three in one call, the pyramid in the ctx's workspace: bit for bit the three calls. */
+int  rcn_sift_detect_and_compute_device(rcn_ctx *ctx, const void *images_dev, int32_t input_dtype, int64_t stride_img, int64_t stride_y,
+                                        int64_t stride_x, int32_t n, int32_t H, int32_t W, const rcn_sift_options *opt, int32_t K,
+                                        float *xy_dev, int32_t *xy_int_dev, float *size_dev, float *angle_dev, float *response_dev,
+                                        int32_t *octave_dev, int32_t *counts_dev, float *rows_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,8 @@ SYMBOLS = [
     "rcn_sg_default_options", "rcn_sg_scores_device", "rcn_sg_assign_device", "rcn_sg_match_device", "rcn_sg_set_chunk_bytes",
     "rcn_sg_net_create", "rcn_sg_net_destroy", "rcn_sg_net_set_chunk_pairs", "rcn_sg_net_forward_device", "rcn_sg_net_match_device",
     "rcn_sp_net_create", "rcn_sp_net_destroy", "rcn_sp_net_set_chunk_images", "rcn_sp_net_forward_device", "rcn_sp_net_detect_device",
+    "rcn_sift_default_options", "rcn_sift_layout", "rcn_sift_set_chunk_images", "rcn_sift_pyramid_device", "rcn_sift_candidates_device", "rcn_sift_detect_device",
+    "rcn_sift_describe_device", "rcn_sift_detect_and_compute_device",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -112,6 +114,18 @@ class TwoViewOptions(C.Structure):
 class SgOptions(C.Structure):
     _fields_ = [("alpha", C.c_double), ("match_threshold", C.c_double), ("score_threshold", C.c_double),
                 ("iterations", C.c_int32), ("path", C.c_int32)]
+
+
+class SiftOptions(C.Structure):
+    _fields_ = [("n_octave_layers", C.c_int32), ("reserved", C.c_int32), ("contrast_threshold", C.c_double),
+                ("edge_threshold", C.c_double), ("sigma", C.c_double)]
+
+
+class SiftLayout(C.Structure):
+    _fields_ = [("n_octaves", C.c_int32), ("n_layers", C.c_int32), ("base_taps", C.c_int32), ("reserved", C.c_int32),
+                ("base_sigma", C.c_double), ("oct_h", C.c_int32 * 16), ("oct_w", C.c_int32 * 16),
+                ("layer_sigma", C.c_double * 8), ("layer_taps", C.c_int32 * 8), ("layer_offset", (C.c_int64 * 8) * 16),
+                ("floats_per_image", C.c_int64)]
 
 
 class BaOptions(C.Structure):
@@ -226,6 +240,24 @@ def load():
     L.rcn_sp_net_forward_device.argtypes = sp_net_in + [vp, vp]
     L.rcn_sp_net_detect_device.restype = C.c_int
     L.rcn_sp_net_detect_device.argtypes = sp_net_in + [i32, C.c_double, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.rcn_sift_default_options.restype = None
+    L.rcn_sift_default_options.argtypes = [C.POINTER(SiftOptions)]
+    L.rcn_sift_layout.restype = C.c_int
+    L.rcn_sift_layout.argtypes = [i32, i32, C.POINTER(SiftOptions), C.POINTER(SiftLayout)]
+    L.rcn_sift_set_chunk_images.restype = C.c_int
+    L.rcn_sift_set_chunk_images.argtypes = [vp, i32]
+    sift_img = [vp, vp, i32, i64, i64, i64, i32, i32, i32, C.POINTER(SiftOptions)]     # ctx, images, dtype, strides, n H W, options
+    sift_kp = [vp, vp, vp, vp, vp, vp, vp]                                              # xy, xy_int, size, angle, response, octave, counts
+    L.rcn_sift_pyramid_device.restype = C.c_int
+    L.rcn_sift_pyramid_device.argtypes = sift_img + [vp]
+    L.rcn_sift_candidates_device.restype = C.c_int
+    L.rcn_sift_candidates_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(SiftOptions), i32, vp, vp]
+    L.rcn_sift_detect_device.restype = C.c_int
+    L.rcn_sift_detect_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(SiftOptions), i32] + sift_kp
+    L.rcn_sift_describe_device.restype = C.c_int
+    L.rcn_sift_describe_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(SiftOptions), i32, vp, vp, vp, vp, vp, vp]
+    L.rcn_sift_detect_and_compute_device.restype = C.c_int
+    L.rcn_sift_detect_and_compute_device.argtypes = sift_img + [i32] + sift_kp + [vp]
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

@@ -160,6 +160,8 @@ struct rcn_ctx {
     int32_t gnn_chunk_pairs = 0;  // pairs per chunk of the graph network (rcn_sg_net_set_chunk_pairs; 0: as many as fit the default cap)
     DevBuf sp_ws, sp_out;     // superpoint_net.hip: the activations of one chunk of images; the logits and descriptor maps of rcn_sp_net_detect_device
     int32_t sp_chunk_images = 0;  // images per chunk of SuperPoint's network (rcn_sp_net_set_chunk_images; 0: as many as fit the default cap)
+    DevBuf sift_ws, sift_pyr; // sift.hip: candidate / keypoint lists and counters of one chunk of images; the pyramids of rcn_sift_detect_and_compute_device
+    int32_t sift_chunk_images = 0;  // images per chunk of the SIFT detector (rcn_sift_set_chunk_images; 0: as many as fit the default cap)
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)

@@ -6,9 +6,11 @@
 //   FeatCoordConf / FeatureConf                   datatypes.h:30-44, 112-136 (SuperPoint: a confidence per keypoint)
 //   TriangulatedFeature / Landmark                datatypes.h:125-183
 //   PinholeCamera                                 Camera.h:12-120 (fX,fY,cX,cY,k1,k2 + project)
+//   GreyImage                                     the cv::Mat a FeatureDetector takes (FeatureDetector.h:28-31): one grey image
 // Only the members the matcher / bundle-adjuster boundary touches are declared.
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <unordered_map>
@@ -61,6 +63,14 @@ struct Landmark {
     Landmark(double x_, double y_, double z_) : x(x_), y(y_), z(z_) {}
     std::vector<TriangulatedFeature> triangulatedFeatures;
     double x = 0, y = 0, z = 0;
+};
+
+// A grey image, row-major, standing in for cv::Mat where a detector takes one: bytes (the detector's input type) or floats on the 0..255 scale
+struct GreyImage {
+    int rows = 0, cols = 0;
+    bool isFloat = false;
+    std::vector<uint8_t> u8;
+    std::vector<float> f32;
 };
 
 // 4x4 row-major double matrix standing in for Eigen::Matrix4d at the boundary: M(r,c).

@@ -83,3 +83,20 @@ def descriptor_set(kind, n_images, K, n_world=None, seed=1234, first_image=0, co
     count = n_images - first_image if count is None else count
     ks = K if hasattr(K, "__len__") else [K] * n_images
     return [image_descriptors(kind, i, ks[i], pool, seed) for i in range(first_image, first_image + count)]
+
+
+def blob_image(H, W, blobs, texture=0.0, seed=0):
+    """Synthetic grey image on the 0..255 scale (float64): anisotropic Gaussian blobs (cx, cy, sigma_x, sigma_y, angle, amplitude) on
+    a mid-grey ground plus a smooth low-amplitude texture.  Non-integer centres keep gradients off the orientation bins' borders."""
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    img = np.full((H, W), 110.0)
+    for cx, cy, sx, sy, th, amp in blobs:
+        u = (xx - cx) * np.cos(th) + (yy - cy) * np.sin(th)
+        v = -(xx - cx) * np.sin(th) + (yy - cy) * np.cos(th)
+        img += amp * np.exp(-0.5 * ((u / sx) ** 2 + (v / sy) ** 2))
+    if texture:
+        rng = np.random.default_rng(seed)
+        for _ in range(6):
+            fx, fy, ph = rng.uniform(0.02, 0.2), rng.uniform(0.02, 0.2), rng.uniform(0, 6.28)
+            img += texture * np.sin(xx * fx * 6.28 + yy * fy * 6.28 + ph)
+    return np.clip(img, 0.0, 255.0)
