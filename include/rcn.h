@@ -987,6 +987,61 @@ int  rcn_sift_detect_and_compute_device(rcn_ctx *ctx, const void *images_dev, in
                                         float *xy_dev, int32_t *xy_int_dev, float *size_dev, float *angle_dev, float *response_dev,
                                         int32_t *octave_dev, int32_t *counts_dev, float *rows_out_dev);
 
+/* ---- retrieval: the ImageMatcher stage (ImageMatcher.h:14-33) by global descriptor ------------------------------------
+ * Which image pairs are matched at all.  The reference ships FakeImgMatcher (ImageMatcher.cpp:6-23: every i != j); this is the
+ * retrieval its README leaves open, built from the local descriptors alone: Lloyd's k-means on the call's own rows (or a
+ * codebook of the caller's), VLAD per image, dense similarities, the top k neighbours per image, and their symmetric pair list
+ * in the order rcn_match_grid takes.  No model and no codebook is shipped.  Defined by tests/retr_ref.py:
+ * fp64 on the fp32 inputs, products rounded before they are added, sums in ascending order; every stage equals it bit for bit.
+ *
+ * desc_dev is the matcher's device layout, [n][K][D] fp32 row-major (rcn_desc_upload_batch_device, rcn_shard_reserve, the
+ * detectors' output); counts_dev[i] rows of image i are in use (clamped to 0..K; NULL: K each), the rest is never read.
+ *
+ *   training rows  row r of image i iff r % s == 0 and r < counts[i], in (image, row) order; s = train_row_stride, or when 0
+ *                  the smallest s with n ceil(K / s) <= 2^18.  M of them; M < n_centroids is an error.
+ *   init           centroid c = training row floor(c M / C)
+ *   Lloyd step     nearest centroid by squared distance (ties: the lowest index); centroid = float(sum of its rows / their
+ *                  number), the sum per image first and over the images then; an empty cluster keeps its centroid.
+ *                  Exactly `iterations` steps.
+ *   VLAD           V[c][d] = sum of the image's rows assigned to c - number * centroid; V' = sign(V) sqrt|V|;
+ *                  G = float(V' / |V'|), zeros for an image without rows.  L = C D floats per image.
+ *   similarity     sim[i][j] = sum over c of (sum over d of G_i[c][d] G_j[c][d]): blocks of D, then the blocks
+ *   neighbours     of image i: the j != i by (sim descending, j ascending), the first min(k, n - 1)
+ *   pairs          (min(i, j), max(i, j)) for j a neighbour of i, as ids first_img_id + slot, ascending, without duplicates.
+ *                  With k >= n - 1 that is the canonical grid (every i < j).
+ *
+ * An image's G does not depend on the batch it is encoded in, on the padding K, or on n.
+ * Limits: 1 <= D <= 256 (RCN_ERR_ARG), C D <= 65536 and n <= 8192 (RCN_ERR_UNSUPPORTED: the similarity matrix is n^2 doubles).
+ * RCN_ERR_ARG: a null pointer, a negative size, a codebook of another D or another ctx, top_k / k < 1, n_centroids < 1,
+ * iterations < 0, train_row_stride < 0.  n == 0 launches nothing.  Rows must be finite.  Asynchronous on the ctx stream except
+ * where noted. */
+typedef struct { int32_t n_centroids, iterations, train_row_stride, top_k, reserved[4]; } rcn_retr_options;
+void rcn_retr_default_options(rcn_retr_options *o);                       /* 64, 10, 0 (automatic), 20 */
+typedef struct rcn_retr_codebook rcn_retr_codebook;
+/* opt == NULL: the defaults (top_k is not used here).  Waits once, for M. */
+int  rcn_retr_codebook_train_device(rcn_ctx *ctx, const float *desc_dev, const int32_t *counts_dev, int32_t n, int32_t K, int32_t D,
+                                    const rcn_retr_options *opt, rcn_retr_codebook **out);
+int  rcn_retr_codebook_create(rcn_ctx *ctx, const float *centroids_host /*[C][D]*/, int32_t C, int32_t D, rcn_retr_codebook **out);
+/* C and D (either may be NULL), and the centroids unless centroids_host is NULL; waits */
+int  rcn_retr_codebook_read(const rcn_retr_codebook *cb, float *centroids_host, int32_t *C, int32_t *D);
+void rcn_retr_codebook_destroy(rcn_retr_codebook *cb);                    /* before its ctx */
+/* rows_dev: [n_rows][D of the codebook]; assign_dev[r]: the nearest centroid of row r */
+int  rcn_retr_assign_device(rcn_ctx *ctx, const rcn_retr_codebook *cb, const float *rows_dev, int64_t n_rows, int32_t *assign_dev);
+int  rcn_retr_encode_device(rcn_ctx *ctx, const rcn_retr_codebook *cb, const float *desc_dev, const int32_t *counts_dev, int32_t n, int32_t K,
+                            int32_t D, float *global_dev /*[n][C*D]*/);
+/* D: the length of a block of the two-level sum (the codebook's D; L a multiple of it) */
+int  rcn_retr_similarity_device(rcn_ctx *ctx, const float *global_dev, int32_t n, int32_t L, int32_t D, double *sim_dev /*[n][n]*/);
+int  rcn_retr_topk_device(rcn_ctx *ctx, const double *sim_dev, int32_t n, int32_t k, int32_t *nbr_dev /*[n][min(k,n-1)], slots*/);
+/* pairs_dev holds `capacity` pairs; *n_pairs_dev receives the length of the list.  Waits for it: RCN_ERR_ARG when the list is
+ * longer than capacity (as rcn_match_compact_begin; the first `capacity` pairs are stored).  An entry of nbr_dev outside
+ * 0 .. n - 1, or an image's own slot, is ignored. */
+int  rcn_retr_pairs_device(rcn_ctx *ctx, const int32_t *nbr_dev, int32_t n, int32_t k, int32_t first_img_id, int32_t *pairs_dev,
+                           int64_t capacity, int32_t *n_pairs_dev);
+/* All stages behind the codebook, the intermediate results in the ctx's workspace; waits.  pairs_host: the list rcn_match_grid
+ * takes, `capacity` pairs; *n_pairs_out its length (RCN_ERR_ARG and nothing copied when capacity is smaller). */
+int  rcn_retr_image_pairs(rcn_ctx *ctx, const rcn_retr_codebook *cb, const float *desc_dev, const int32_t *counts_dev, int32_t n, int32_t K,
+                          int32_t D, int32_t first_img_id, int32_t top_k, int32_t *pairs_host, int64_t capacity, int32_t *n_pairs_out);
+
 #ifdef __cplusplus
 }
 #endif

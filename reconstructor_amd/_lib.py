@@ -43,6 +43,8 @@ SYMBOLS = [
     "rcn_sp_net_create", "rcn_sp_net_destroy", "rcn_sp_net_set_chunk_images", "rcn_sp_net_forward_device", "rcn_sp_net_detect_device",
     "rcn_sift_default_options", "rcn_sift_layout", "rcn_sift_set_chunk_images", "rcn_sift_pyramid_device", "rcn_sift_candidates_device", "rcn_sift_detect_device",
     "rcn_sift_describe_device", "rcn_sift_detect_and_compute_device",
+    "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
+    "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -126,6 +128,11 @@ class SiftLayout(C.Structure):
                 ("base_sigma", C.c_double), ("oct_h", C.c_int32 * 16), ("oct_w", C.c_int32 * 16),
                 ("layer_sigma", C.c_double * 8), ("layer_taps", C.c_int32 * 8), ("layer_offset", (C.c_int64 * 8) * 16),
                 ("floats_per_image", C.c_int64)]
+
+
+class RetrOptions(C.Structure):
+    _fields_ = [("n_centroids", C.c_int32), ("iterations", C.c_int32), ("train_row_stride", C.c_int32), ("top_k", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class BaOptions(C.Structure):
@@ -258,6 +265,28 @@ def load():
     L.rcn_sift_describe_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(SiftOptions), i32, vp, vp, vp, vp, vp, vp]
     L.rcn_sift_detect_and_compute_device.restype = C.c_int
     L.rcn_sift_detect_and_compute_device.argtypes = sift_img + [i32] + sift_kp + [vp]
+    L.rcn_retr_default_options.restype = None
+    L.rcn_retr_default_options.argtypes = [C.POINTER(RetrOptions)]
+    L.rcn_retr_codebook_train_device.restype = C.c_int
+    L.rcn_retr_codebook_train_device.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(RetrOptions), C.POINTER(vp)]
+    L.rcn_retr_codebook_create.restype = C.c_int
+    L.rcn_retr_codebook_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
+    L.rcn_retr_codebook_read.restype = C.c_int
+    L.rcn_retr_codebook_read.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.rcn_retr_codebook_destroy.restype = None
+    L.rcn_retr_codebook_destroy.argtypes = [vp]
+    L.rcn_retr_assign_device.restype = C.c_int
+    L.rcn_retr_assign_device.argtypes = [vp, vp, vp, i64, vp]
+    L.rcn_retr_encode_device.restype = C.c_int
+    L.rcn_retr_encode_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.rcn_retr_similarity_device.restype = C.c_int
+    L.rcn_retr_similarity_device.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.rcn_retr_topk_device.restype = C.c_int
+    L.rcn_retr_topk_device.argtypes = [vp, vp, i32, i32, vp]
+    L.rcn_retr_pairs_device.restype = C.c_int
+    L.rcn_retr_pairs_device.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp]
+    L.rcn_retr_image_pairs.restype = C.c_int
+    L.rcn_retr_image_pairs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, C.POINTER(i32)]
     L.rcn_desc_clear.restype = C.c_int
     L.rcn_desc_clear.argtypes = [vp]
     L.rcn_desc_count.restype = C.c_int

@@ -162,6 +162,7 @@ struct rcn_ctx {
     int32_t sp_chunk_images = 0;  // images per chunk of SuperPoint's network (rcn_sp_net_set_chunk_images; 0: as many as fit the default cap)
     DevBuf sift_ws, sift_pyr; // sift.hip: candidate / keypoint lists and counters of one chunk of images; the pyramids of rcn_sift_detect_and_compute_device
     int32_t sift_chunk_images = 0;  // images per chunk of the SIFT detector (rcn_sift_set_chunk_images; 0: as many as fit the default cap)
+    DevBuf retr_ws, retr_out; // retrieval.hip: assignments, segment sums and counts, the pair mask; global descriptors, similarities and lists of rcn_retr_image_pairs
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)

@@ -7,10 +7,12 @@
 //   TriangulatedFeature / Landmark                datatypes.h:125-183
 //   PinholeCamera                                 Camera.h:12-120 (fX,fY,cX,cY,k1,k2 + project)
 //   GreyImage                                     the cv::Mat a FeatureDetector takes (FeatureDetector.h:28-31): one grey image
+//   ImageMatcher                                  ImageMatcher.h:14-22: the plugin that decides which image pairs are matched
 // Only the members the matcher / bundle-adjuster boundary touches are declared.
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <filesystem>
 #include <map>
 #include <memory>
 #include <unordered_map>
@@ -71,6 +73,16 @@ struct GreyImage {
     bool isFloat = false;
     std::vector<uint8_t> u8;
     std::vector<float> f32;
+};
+
+// Which images are matched against which: imgMatches[id] lists the partners of image id (the reference ships FakeImgMatcher, every
+// other image; HipImageMatcher.h retrieves them).
+class ImageMatcher {
+public:
+    virtual void match(const std::unordered_map<int, std::filesystem::path> &imgIds2Paths,
+                       const std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                       std::unordered_map<int, std::vector<int>> &imgMatches) = 0;
+    virtual ~ImageMatcher() {}
 };
 
 // 4x4 row-major double matrix standing in for Eigen::Matrix4d at the boundary: M(r,c).
