@@ -18,6 +18,7 @@
 // The LM control flow on the host follows Ceres' TrustRegionMinimizer / LevenbergMarquardt
 // strategy step by step (same order of tests as the CPU restatement used for parity).
 #include "rcn_internal.h"
+#include "wgprim.h"
 #include <utility>
 #include "ba_linesearch.h"
 
@@ -673,50 +674,29 @@ __global__ __launch_bounds__(256) void k_pair_count(BaDev d, int *cnt)
     }
 }
 
-// exclusive scan of n ints (n ~ nc^2) in three coalesced passes: per-chunk sums (one workgroup
-// per 1024-element chunk), scan of the chunk sums by one workgroup, per-chunk scan with offset
-__device__ __forceinline__ int block_scan_1024(int v, int *sh)   // inclusive scan over the workgroup's 1024 threads
-{
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o); if (lane >= o) v += u; }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    if (t < 16) { int s = sh[t]; for (int o = 1; o < 16; o <<= 1) { const int u = __shfl_up(s, o, 16); if (t >= o) s += u; } sh[t] = s; }
-    __syncthreads();
-    const int base = w ? sh[w - 1] : 0;
-    __syncthreads();
-    return v + base;
-}
+// exclusive scan of n ints (n ~ nc^2) in three passes: per-chunk sums (one workgroup per 1024-element chunk, coalesced),
+// scan of the chunk sums by one workgroup (in place; a contiguous run per thread once there are more than 1024 chunks),
+// per-chunk scan with offset (coalesced)
 __global__ __launch_bounds__(1024) void k_scan_sums(const int *in, int *sums, int n)
 {
     __shared__ int sh[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
-    const int tot = block_scan_1024(i < n ? in[i] : 0, sh);
+    int tot;
+    (void)wg_scan_incl<int, 1024>(i < n ? in[i] : 0, sh, tot);
     if (threadIdx.x == 1023) sums[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(1024) void k_scan_top(int *sums, int nchunks, int *total)   // nchunks <= 1024*1024
+__global__ __launch_bounds__(1024) void k_scan_top(int *sums, int nchunks, int *total)   // in place
 {
-    __shared__ int sh[16];
-    int carry = 0;
-    for (int b = 0; b < nchunks; b += 1024) {
-        const int i = b + threadIdx.x;
-        const int v = i < nchunks ? sums[i] : 0;
-        const int inc = block_scan_1024(v, sh);
-        if (i < nchunks) sums[i] = carry + inc - v;      // exclusive
-        __shared__ int last;
-        if (threadIdx.x == 1023) last = inc;
-        __syncthreads();
-        carry += last;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+    const int tot = wg_scan_array(sums, nchunks, sums, 0);
+    if (threadIdx.x == 0) *total = tot;
 }
 __global__ __launch_bounds__(1024) void k_scan_apply(const int *in, const int *sums, int *out, int n)
 {
     __shared__ int sh[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
     const int v = i < n ? in[i] : 0;
-    const int inc = block_scan_1024(v, sh);
+    int tot;
+    const int inc = wg_scan_incl<int, 1024>(v, sh, tot);
     if (i < n) out[i] = sums[blockIdx.x] + inc - v;
 }
 
@@ -754,9 +734,10 @@ __global__ __launch_bounds__(1024) void k_pair_small(BaDev d, int *off, unsigned
     }
     __syncthreads();
     const int v = t < nkeys ? cnt[t] : 0;
-    const int inc = block_scan_1024(v, sh);
+    int tot;
+    const int inc = wg_scan_incl<int, 1024>(v, sh, tot);
     if (t < nkeys) off[t] = inc - v;
-    if (t == 1023) off[nkeys] = inc;
+    if (t == 1023) off[nkeys] = tot;
     __syncthreads();
     cnt[t] = inc - v;
     __syncthreads();

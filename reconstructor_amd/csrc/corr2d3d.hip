@@ -24,6 +24,7 @@
 // camgeom.h reproj_l1) depth > 0, L1 error < max, then the first PASSING entry of every feature wins -- the smallest
 // entry index by atomicMin, which is order-independent.
 #include "camgeom.h"
+#include "wgprim.h"
 
 #include <algorithm>
 #include <climits>
@@ -139,33 +140,18 @@ __global__ __launch_bounds__(CB) void k_corr_count(const int32_t *__restrict__ h
 __global__ __launch_bounds__(1024) void k_corr_scan(const int32_t *__restrict__ cnt, int n, int bpr, int64_t *__restrict__ off,
                                                     int64_t *__restrict__ base, int64_t *__restrict__ cand_off)
 {
-    __shared__ int64_t part[1024];
-    const int t = threadIdx.x, per = (n + 1023) / 1024, b0 = min(n, t * per), b1 = min(n, b0 + per);
-    const int64_t b = *base;                       // read by every thread before the syncs below; written after them
-    int64_t s = 0;
-    for (int q = b0; q < b1; ++q) s += cnt[q];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int64_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    s = b + (t ? part[t - 1] : 0);
-    for (int q = b0; q < b1; ++q) {
-        off[q] = s;
-        if (q % bpr == 0) cand_off[q / bpr] = s;
-        s += cnt[q];
-    }
-    if (t == 1023) *base = b + part[1023];
+    const int t = threadIdx.x;
+    const int64_t end = wg_scan_array(cnt, n, off, *base);      // *base: read by every thread before the scan's barriers; written after them
+    if (t == 1023) *base = end;
+    __syncthreads();                                             // off was written by other threads of this workgroup
+    for (int k = t; k * (int64_t)bpr < n; k += 1024) cand_off[k] = off[k * (int64_t)bpr];
 }
 
 __global__ __launch_bounds__(CB) void k_corr_compact(const int32_t *__restrict__ hit, int64_t ld, const int32_t *__restrict__ blk_cnt,
                                                      const int64_t *__restrict__ blk_off, const int32_t *__restrict__ obs_pt,
                                                      int64_t cap, int32_t *__restrict__ out_lm, int32_t *__restrict__ out_feat)
 {
-    __shared__ int32_t sh[CB];
+    __shared__ int32_t sh[CB / 64];
     const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (blk_cnt[tile] == 0) return;                 // uniform over the workgroup
     const int t = threadIdx.x;
@@ -175,15 +161,8 @@ __global__ __launch_bounds__(CB) void k_corr_compact(const int32_t *__restrict__
     int n = 0;
 #pragma unroll
     for (int j = 0; j < CPT; ++j) n += v[j] >= 0;
-    sh[t] = n;
-    __syncthreads();
-    for (int d = 1; d < CB; d <<= 1) {               // inclusive scan of the thread counts
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    int64_t pos = blk_off[tile] + sh[t] - n;
+    int32_t in_tile;
+    int64_t pos = blk_off[tile] + wg_scan_incl<int32_t, CB>(n, sh, in_tile) - n;
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
         if (v[j] < 0) continue;
@@ -420,7 +399,7 @@ __global__ __launch_bounds__(CB) void k_pair_fill(const PairFill *__restrict__ p
                                                   int32_t *__restrict__ qt)
 {
     __shared__ int32_t wtot[CB / 64];
-    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int p = blockIdx.x, t = threadIdx.x;
     if (cnt[p] <= 0) return;                             // uniform
     const PairFill q = pf[p];
     const SlotDev sa = slots[q.sa], sb = slots[q.sb];
@@ -430,18 +409,14 @@ __global__ __launch_bounds__(CB) void k_pair_fill(const PairFill *__restrict__ p
     for (int f0 = 0; f0 < sa.K; f0 += CB) {
         const int f = f0 + t;
         const int g = f < sa.K ? row[f] : -1;
-        const unsigned long long b = __ballot(g >= 0);
-        if (lane == 0) wtot[wv] = (int32_t)__popcll(b);
-        __syncthreads();
-        int64_t pos = run + (int64_t)__popcll(b & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wv; ++w) pos += wtot[w];
+        int chunk;
+        const int64_t pos = run + wg_rank<CB>(g >= 0, wtot, chunk);
         if (g >= 0 && pos < end) {
             xy1[2 * pos] = sa.xy[2 * (size_t)f]; xy1[2 * pos + 1] = sa.xy[2 * (size_t)f + 1];
             xy2[2 * pos] = sb.xy[2 * (size_t)g]; xy2[2 * pos + 1] = sb.xy[2 * (size_t)g + 1];
             if (qt) { qt[2 * pos] = f; qt[2 * pos + 1] = g; }
         }
-        run += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-        __syncthreads();
+        run += chunk;
     }
 }
 

@@ -11,6 +11,8 @@
 //   F1-F5  round-synchronous RANSAC / LMedS, every phase its own launch over ALL pairs (see the
 //          comment above FmState): begin -> [solve -> score -> accept] x 32 -> finish.       [fp64 VALU]
 #include "rcn_internal.h"
+#include "ransac.h"
+#include "wgprim.h"
 
 #include <cfloat>
 #include <string>
@@ -30,25 +32,6 @@ struct FmatArgs {
     int32_t *counts, *iters;
     double *F;   // optional: the winning matrix of every pair, 9 doubles (zeros when there is none)
 };
-
-__device__ __forceinline__ unsigned rng_next(unsigned long long &s)
-{
-    s = (unsigned long long)(unsigned)s * 4164903690U + (unsigned)(s >> 32);
-    return (unsigned)s;
-}
-
-__device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters)
-{
-#pragma clang fp contract(off)
-    p = fmax(p, 0.); p = fmin(p, 1.);
-    ep = fmax(ep, 0.); ep = fmin(ep, 1.);
-    double num = fmax(1. - p, DBL_MIN);
-    double denom = 1. - pow(1. - ep, (double)model_points);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)lrint(num / denom);
-}
 
 __device__ int solve_cubic(const double *c, double *r)
 {
@@ -714,40 +697,8 @@ namespace {
 
 __global__ __launch_bounds__(1024) void k_tf_scan(const int32_t *counts, int n, int32_t *off)
 {
-    __shared__ int sh[16];
-    __shared__ int carry_s;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int carry = 0;
-    if (t == 0) off[0] = 0;
-    for (int b = 0; b < n; b += 1024) {
-        const int i = b + t;
-        int v = i < n ? counts[i] : 0;
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o); if (lane >= o) v += u; }
-        if (lane == 63) sh[w] = v;
-        __syncthreads();
-        if (t < 16) { int s = sh[t]; for (int o = 1; o < 16; o <<= 1) { const int u = __shfl_up(s, o, 16); if (t >= o) s += u; } sh[t] = s; }
-        __syncthreads();
-        const int incl = v + (w ? sh[w - 1] : 0) + carry;
-        if (i < n) off[i + 1] = incl;
-        if (t == 1023) carry_s = incl;
-        __syncthreads();
-        carry = carry_s;
-        __syncthreads();
-    }
-}
-
-// ordered position of each flagged thread within the workgroup's 256-wide chunk; returns the chunk total
-__device__ __forceinline__ int chunk_rank(bool flag, int &rank, int *sh)
-{
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) sh[w] = (int)__popcll(m);
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int i = 0; i < 4; ++i) { base += i < w ? sh[i] : 0; total += sh[i]; }
-    rank = base + (int)__popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();
-    return total;
+    const int32_t total = wg_scan_array(counts, n, off, (int32_t)0);
+    if (threadIdx.x == 1023) off[n] = total;
 }
 
 __global__ __launch_bounds__(256) void k_tf_fill(const PairXY *px, const int32_t *table, int64_t stride, const int32_t *off,
@@ -761,8 +712,8 @@ __global__ __launch_bounds__(256) void k_tf_fill(const PairXY *px, const int32_t
     for (int q0 = 0; q0 < p.Kq; q0 += 256) {
         const int q = q0 + t;
         const int tr = q < p.Kq ? row[q] : -1;
-        int rank;
-        const int total = chunk_rank(tr >= 0, rank, sh);
+        int total;
+        const int rank = wg_rank<256>(tr >= 0, sh, total);
         if (tr >= 0) {
             const size_t o = 2 * (size_t)(pos + rank);
             xy1[o] = p.q[2 * q]; xy1[o + 1] = p.q[2 * q + 1];
@@ -785,8 +736,8 @@ __global__ __launch_bounds__(256) void k_tf_apply(const PairXY *px, int32_t *tab
     for (int q0 = 0; q0 < p.Kq; q0 += 256) {
         const int q = q0 + t;
         const int tr = q < p.Kq ? row[q] : -1;
-        int rank;
-        const int total = chunk_rank(tr >= 0, rank, sh);
+        int total;
+        const int rank = wg_rank<256>(tr >= 0, sh, total);
         if (tr >= 0 && (v < 0 || !mask[pos + rank])) row[q] = -1;
         pos += total;
     }

@@ -12,6 +12,7 @@
 // Canonical order: confidence descending, raster index ascending; as a key (fp32 bits << 32) | (2^31 - 1 - raster),
 // larger first.  The heat stage carries a tolerance (expf, the order of sums); everything behind it is exact.
 #include "rcn_internal.h"
+#include "wgprim.h"
 
 #include <algorithm>
 
@@ -164,25 +165,6 @@ __device__ __forceinline__ unsigned long long kp_key(float conf, unsigned q)
 // pixels of a status word whose two bits say "kept" (10), as a mask on the even bits
 __device__ __forceinline__ unsigned kp_kept(unsigned w) { return (w >> 1) & ~w & 0x55555555u; }
 
-__device__ __forceinline__ int kp_block_scan(int v, int (*s)[KP_BLOCK], int *total)
-{
-    const int tid = threadIdx.x;
-    int in = 0;
-    s[0][tid] = v;
-    __syncthreads();
-    for (int off = 1; off < KP_BLOCK; off <<= 1) {
-        int t = s[in][tid];
-        if (tid >= off) t += s[in][tid - off];
-        s[1 - in][tid] = t;
-        __syncthreads();
-        in = 1 - in;
-    }
-    const int incl = s[in][tid];
-    *total = s[in][KP_BLOCK - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 // One workgroup per image.  Status, two bits per pixel, 16 pixels per word: 00 no candidate / suppressed (a suppressed
 // candidate kills nothing and blocks nobody: the same as none), 01 undecided, 10 kept; 11 only inside a round (kept, not yet
 // published: read as undecided).  A round: phase A reads the status as the last round left it -- an undecided candidate
@@ -192,7 +174,7 @@ __device__ __forceinline__ int kp_block_scan(int v, int (*s)[KP_BLOCK], int *tot
 __global__ __launch_bounds__(KP_BLOCK) void k_kp_nms(KpNmsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned kp_smem[];
-    __shared__ int s_scan[2][KP_BLOCK];
+    __shared__ int s_scan[KP_BLOCK / 64];
     __shared__ unsigned s_hist[256];
     __shared__ int s_any, s_remaining;
     __shared__ unsigned long long s_prefix;
@@ -280,7 +262,7 @@ __global__ __launch_bounds__(KP_BLOCK) void k_kp_nms(KpNmsArgs a)
         mine += __popc(keep);
     }
     int total;
-    (void)kp_block_scan(mine, s_scan, &total);
+    (void)wg_scan_incl<int, KP_BLOCK>(mine, s_scan, total);
     if (tid == 0) {
         a.counts[img] = total;
         if (a.rounds) a.rounds[img] = (int32_t)rounds;
@@ -334,7 +316,7 @@ __global__ __launch_bounds__(KP_BLOCK) void k_kp_nms(KpNmsArgs a)
     mine = 0;
     for (int w = w0; w < w1; ++w) mine += __popc(kp_kept(kp_ld(&st[w])));
     int kept;
-    int pos = kp_block_scan(mine, s_scan, &kept);
+    int pos = wg_scan_incl<int, KP_BLOCK>(mine, s_scan, kept) - mine;
     int32_t *xy = a.xy + (size_t)img * K * 2;
     float *conf = a.conf ? a.conf + (size_t)img * K : nullptr;
     for (int w = w0; w < w1; ++w) {

@@ -27,9 +27,9 @@
 // entry is one kernel launch on the ctx stream: no host wait, no device-to-host copy, and no allocation once the table's
 // buffer is sized (it grows only with the span of uploaded image ids).  The kernel needs no workspace in HBM.
 //
-// rng_next and update_num_iters are copies of fmat.hip's (three short functions; fmat.hip is untouched).
+// rng_next, update_num_iters and finite_d are ransac.h's, shared with the other two searches.
 #include "camgeom.h"
-#include <cfloat>
+#include "ransac.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -65,25 +65,6 @@ struct PnpArgs {
 
 struct Entry { double x, y, z; int32_t ox, oy; };
 
-__device__ __forceinline__ unsigned rng_next(unsigned long long &s)
-{
-    s = (unsigned long long)(unsigned)s * 4164903690U + (unsigned)(s >> 32);
-    return (unsigned)s;
-}
-
-__device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters)
-{
-#pragma clang fp contract(off)
-    p = fmax(p, 0.); p = fmin(p, 1.);
-    ep = fmax(ep, 0.); ep = fmin(ep, 1.);
-    double num = fmax(1. - p, DBL_MIN);
-    double denom = 1. - pow(1. - ep, (double)model_points);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)lrint(num / denom);
-}
-
 // the view's entries: LDS, or the arrays themselves
 struct View {
     const Entry *lds;           // NULL: read through the indices
@@ -114,7 +95,6 @@ __device__ __forceinline__ void cross3(const double *a, const double *b, double 
 {
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ bool finite_d(double x) { return x - x == 0.0; }
 __device__ __forceinline__ double pymax(double a, double b) { return b > a ? b : a; }
 
 // Camera.h:79-93 unprojection of the pixel, normalised

@@ -15,6 +15,7 @@
 //   k_retr_topk           one workgroup per image, rank by counting
 //   k_retr_pairs_*        neighbour table -> n x n mask -> per-row counts -> prefix -> ascending list
 #include "rcn_internal.h"
+#include "wgprim.h"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -308,12 +309,10 @@ __global__ __launch_bounds__(64) void k_retr_pairs_rows(const uint8_t *mask, int
     if (!FILL && lane == 0) rowcnt[a] = (int32_t)base;
 }
 
-__global__ void k_retr_pairs_scan(const int32_t *rowcnt, int32_t n, long long *rowoff, int32_t *n_pairs)
+__global__ __launch_bounds__(1024) void k_retr_pairs_scan(const int32_t *rowcnt, int32_t n, long long *rowoff, int32_t *n_pairs)
 {
-    if (threadIdx.x || blockIdx.x) return;
-    long long p = 0;
-    for (int a = 0; a < n; ++a) { rowoff[a] = p; p += rowcnt[a]; }
-    *n_pairs = (int32_t)p;                                    // at most n (n - 1) / 2 < 2^25
+    const long long p = wg_scan_array(rowcnt, n, rowoff, 0ll);
+    if (threadIdx.x == 0) *n_pairs = (int32_t)p;              // at most n (n - 1) / 2 < 2^25
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -458,7 +457,7 @@ int retr_pairs(rcn_ctx *ctx, const int32_t *nbr, int32_t n, int32_t kk, int32_t 
     RCN_HIP(hipMemsetAsync(mask, 0, nn, ctx->stream));
     k_retr_pairs_mark<<<(unsigned)(((int64_t)n * kk + 255) / 256), 256, 0, ctx->stream>>>(nbr, n, kk, mask);
     k_retr_pairs_rows<false><<<(unsigned)n, 64, 0, ctx->stream>>>(mask, n, rowcnt, nullptr, first_img_id, nullptr, 0);
-    k_retr_pairs_scan<<<1, 64, 0, ctx->stream>>>(rowcnt, n, rowoff, n_pairs);
+    k_retr_pairs_scan<<<1, 1024, 0, ctx->stream>>>(rowcnt, n, rowoff, n_pairs);
     k_retr_pairs_rows<true><<<(unsigned)n, 64, 0, ctx->stream>>>(mask, n, nullptr, rowoff, first_img_id, pairs, capacity);
     RCN_HIP(hipGetLastError());
     return RCN_OK;

@@ -15,6 +15,7 @@
 //     that computed them.  No other exchange.
 // Every rank converts with the same global scale, so the tables are bit-identical to a one-GPU run.
 #include "rcn_internal.h"
+#include "wgprim.h"
 
 #include <rccl/rccl.h>
 
@@ -732,25 +733,10 @@ __global__ void k_g_canon_counts(const int32_t *__restrict__ rcnt, int world, lo
 // 1024-thread exclusive scan, one block per segment (segment s: counts + s * stride, n entries -> off + s * (stride + 1))
 __global__ __launch_bounds__(1024) void k_g_scan(const int32_t *__restrict__ counts, long stride, long n, long long *__restrict__ off)
 {
-    __shared__ long long sh[1024];
     counts += (size_t)blockIdx.x * stride;
     off += (size_t)blockIdx.x * (stride + 1);
-    const int t = threadIdx.x;
-    const long per = (n + 1023) / 1024;
-    const long lo = min(n, t * per), hi = min(n, lo + per);
-    long long s = 0;
-    for (long i = lo; i < hi; ++i) s += counts[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const long long v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    long long run = sh[t] - s;
-    for (long i = lo; i < hi; ++i) { off[i] = run; run += counts[i]; }
-    if (t == 1023) off[n] = sh[1023];
+    const long long total = wg_scan_array(counts, n, off, 0ll);
+    if (threadIdx.x == 1023) off[n] = total;
 }
 // one wave per canonical pair: its entries from the sender's segment to their place in the merged list
 __global__ __launch_bounds__(256) void k_g_interleave(const int2 *__restrict__ recv, const long long *__restrict__ disp, const long long *__restrict__ loff,

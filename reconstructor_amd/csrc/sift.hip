@@ -16,6 +16,7 @@
 //   descriptor   k_sift_describe: one wavefront per keypoint over its sample window, the 4 x 4 x 8 (+ border) histogram by
 //                the same fixed-point atomics, normalisation in a fixed order.
 #include "rcn_internal.h"
+#include "wgprim.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -340,26 +341,9 @@ __device__ __forceinline__ int sift_cmp(const SiftKp &a, const SiftKp &b)
     return 0;
 }
 
-__device__ __forceinline__ int sift_scan(int v, int *s, int *total)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int t = tid >= off ? s[tid - off] : 0;
-        __syncthreads();
-        s[tid] += t;
-        __syncthreads();
-    }
-    const int incl = s[tid];
-    *total = s[1023];
-    return incl - v;
-}
-
 __global__ __launch_bounds__(1024) void k_sift_select(SiftSelArgs a)
 {
-    __shared__ int s_scan[1024];
+    __shared__ int s_scan[16];
     const int img = blockIdx.x, tid = threadIdx.x, K = a.K;
     const SiftKp *kp = a.kps + (size_t)img * a.cap;
     unsigned *ord = a.ord + (size_t)img * a.cap, *uniq = a.uniq + (size_t)img * a.cap, *keep = a.keep + (size_t)img * a.cap;
@@ -387,7 +371,7 @@ __global__ __launch_bounds__(1024) void k_sift_select(SiftSelArgs a)
         mine += (p == 0 || !sift_same(kp[cur], kp[prev])) ? 1 : 0;
     }
     int M;
-    int pos = sift_scan(mine, s_scan, &M);
+    int pos = wg_scan_incl<int, 1024>(mine, s_scan, M) - mine;
     for (int p = p0; p < p1; ++p) {
         const unsigned cur = min(ord[p], (unsigned)(N - 1)), prev = p ? min(ord[p - 1], (unsigned)(N - 1)) : 0u;
         if (p == 0 || !sift_same(kp[cur], kp[prev])) uniq[pos++] = cur;
@@ -412,7 +396,7 @@ __global__ __launch_bounds__(1024) void k_sift_select(SiftSelArgs a)
     p0 = min(M, tid * per2); p1 = min(M, p0 + per2); mine = 0;
     for (int p = p0; p < p1; ++p) mine += (int)keep[p];
     int E;
-    pos = sift_scan(mine, s_scan, &E);
+    pos = wg_scan_incl<int, 1024>(mine, s_scan, E) - mine;
     for (int p = p0; p < p1; ++p)
         if (keep[p]) {
             const SiftKp k = kp[uniq[p]];

@@ -8,6 +8,7 @@
 //                        the "features / matches cache" the reference lists as a TODO (README.md:39),
 //                        i.e. the resume point between the matching stage and the reconstruction
 #include "rcn_internal.h"
+#include "wgprim.h"
 
 #include <cerrno>
 #include <cstdio>
@@ -19,23 +20,8 @@ namespace {
 // exclusive scan of the per-pair counts (int32) into int64 offsets; one workgroup, n up to millions
 __global__ __launch_bounds__(1024) void k_cmp_scan(const int32_t *__restrict__ counts, int n, long long *__restrict__ off)
 {
-    __shared__ long long sh[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = min(n, t * per), hi = min(n, lo + per);
-    long long s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const long long v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    long long run = sh[t] - s;
-    for (int i = lo; i < hi; ++i) { off[i] = run; run += counts[i]; }
-    if (t == 1023) off[n] = sh[1023];
+    const long long total = wg_scan_array(counts, n, off, 0ll);
+    if (threadIdx.x == 1023) off[n] = total;
 }
 
 // one workgroup per pair: ordered compaction of the row (ascending query index) by ballots
@@ -44,7 +30,7 @@ __global__ __launch_bounds__(256) void k_cmp_fill(const int32_t *__restrict__ ta
                                                   int2 *__restrict__ qt)
 {
     __shared__ int wsum[4];
-    const int pair = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int pair = blockIdx.x, t = threadIdx.x;
     const int total = counts[pair];
     if (total <= 0) return;
     const int32_t *row = table + (size_t)pair * stride;
@@ -53,17 +39,12 @@ __global__ __launch_bounds__(256) void k_cmp_fill(const int32_t *__restrict__ ta
     for (int64_t q0 = 0; q0 < stride && pos < total; q0 += 256) {
         const int64_t q = q0 + t;
         const int tr = q < stride ? row[q] : -1;
-        const unsigned long long m = __ballot(tr >= 0);
-        if (lane == 0) wsum[w] = (int)__popcll(m);
-        __syncthreads();
-        int base = pos;
-        for (int i = 0; i < w; ++i) base += wsum[i];
+        int chunk;
+        const int at = pos + wg_rank<256>(tr >= 0, wsum, chunk);
         // never past the pair's range: a table whose non-negative entries outnumber counts[pair] (not yet through the
         // uniqueness pass, stale counts) loses its surplus instead of overwriting the next pair's list
-        const int at = base + (int)__popcll(m & ((1ull << lane) - 1ull));
         if (tr >= 0 && at < total) dst[at] = make_int2((int)q, tr);
-        pos += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
+        pos += chunk;
     }
 }
 

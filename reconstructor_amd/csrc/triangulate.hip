@@ -21,6 +21,7 @@
 // last ulp the device library and a host libm may round differently: a decision can differ only for a track at exactly
 // the threshold.
 #include "camgeom.h"
+#include "wgprim.h"
 
 namespace {
 
@@ -173,35 +174,19 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_triangulate(TriArgs a)
 // exclusive scan of n block counts in one workgroup of 1024 threads: thread t owns a contiguous run of ceil(n / 1024)
 __global__ __launch_bounds__(1024) void k_tri_scan(const int32_t *__restrict__ cnt, int n, int32_t *__restrict__ off, int32_t *__restrict__ total)
 {
-    __shared__ int32_t part[1024];
-    const int t = threadIdx.x, per = (n + 1023) / 1024, b0 = min(n, t * per), b1 = min(n, b0 + per);
-    int32_t s = 0;
-    for (int b = b0; b < b1; ++b) s += cnt[b];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                 // inclusive Hillis-Steele scan of the run sums
-        const int32_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    s = t ? part[t - 1] : 0;
-    for (int b = b0; b < b1; ++b) { off[b] = s; s += cnt[b]; }
-    if (t == 1023) *total = part[1023];
+    const int32_t sum = wg_scan_array(cnt, n, off, (int32_t)0);
+    if (threadIdx.x == 1023) *total = sum;
 }
 
 __global__ __launch_bounds__(TRI_BLOCK) void k_tri_compact(const uint8_t *__restrict__ status, const double *__restrict__ xyz, int n,
                                                         const int32_t *__restrict__ blk_off, double *__restrict__ out, int32_t first)
 {
     __shared__ int32_t wave_cnt[TRI_BLOCK / 64];
-    const int j = blockIdx.x * TRI_BLOCK + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int j = blockIdx.x * TRI_BLOCK + threadIdx.x;
     const bool acc = j < n && status[j] == 0;
-    const unsigned long long m = __ballot(acc);
-    if (lane == 0) wave_cnt[w] = (int32_t)__popcll(m);
-    __syncthreads();
+    int in_block;
+    const int32_t r = blk_off[blockIdx.x] + wg_rank<TRI_BLOCK>(acc, wave_cnt, in_block);
     if (!acc) return;
-    int32_t r = blk_off[blockIdx.x] + (int32_t)__popcll(m & ((1ull << lane) - 1));
-    for (int v = 0; v < w; ++v) r += wave_cnt[v];
     const size_t d = 3 * ((size_t)first + (size_t)r);
     out[d] = xyz[3 * (size_t)j]; out[d + 1] = xyz[3 * (size_t)j + 1]; out[d + 2] = xyz[3 * (size_t)j + 2];
 }

@@ -27,10 +27,10 @@
 // tests/twoview_ref.py restates that order and agrees bit for bit.  The one exception is pow / log in update_num_iters.
 // The result depends neither on TV_B nor on the launch geometry.
 //
-// rng_next and update_num_iters are copies of fmat.hip's (fmat.hip and pnp.hip are untouched).
+// rng_next, update_num_iters and finite_d are ransac.h's, shared with the other two searches.
 #include "rcn_internal.h"
+#include "ransac.h"
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -60,27 +60,6 @@ struct TvArgs {
     uint8_t *mask, *cmask;
     int32_t *count, *iters;
 };
-
-__device__ __forceinline__ unsigned rng_next(unsigned long long &s)
-{
-    s = (unsigned long long)(unsigned)s * 4164903690U + (unsigned)(s >> 32);
-    return (unsigned)s;
-}
-
-__device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters)
-{
-#pragma clang fp contract(off)
-    p = fmax(p, 0.); p = fmin(p, 1.);
-    ep = fmax(ep, 0.); ep = fmin(ep, 1.);
-    double num = fmax(1. - p, DBL_MIN);
-    double denom = 1. - pow(1. - ep, (double)model_points);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)lrint(num / denom);
-}
-
-__device__ __forceinline__ bool finite_d(double x) { return x - x == 0.0; }
 
 // Camera.h:79-93 unprojection of the pixel, scaled back by the mean camera matrix Km and normalised by it again
 __device__ __forceinline__ void normalise(const double *K, const double *Km, int32_t ou, int32_t ov, double *x_out, double *y_out)
