@@ -930,7 +930,6 @@ __global__ __launch_bounds__(512) void k_ba_schur_mfma_wg(BaDev d, const int *of
     }
 }
 
-#define RCN_RHS_BETA 1.0e200
 // diagonal blocks: one 16-wave workgroup per camera; wave w takes the observations w, w+16, ... of
 // the camera (a pair (o, o)) and the listed pairs of the key (c, c); the 16 partial blocks are
 // summed in wave order and  scaled U + D/radius  is added before the store into S; column 10 of

@@ -13,6 +13,9 @@ struct rcn_ctx;
 namespace chol {
 constexpr int BLOCK = 128;      // block size: a system is padded to a multiple of it
 }
+// rhs_row: the diagonal entry under the right-hand side in row n of the padded system.  Huge, so that the row's own pivot stays positive
+// whatever b' S^-1 b is; nobody reads what the factorisation leaves there.
+#define RCN_RHS_BETA 1.0e200
 
 // Everything a context keeps for the factorisation: parameters, switches, streams, events, the plan of the last shape.
 struct CholState {

@@ -1372,13 +1372,15 @@ hipError_t rcn_chol_factorise(rcn_ctx *ctx, const CholSystem &s, bool safe)
         case chol::UPD_PIPE: {
             if (op.small) { k_gemm_qm<1><<<16 * op.map_n, 256, 0, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, op.nst / 16, nullptr, 0, gk, op.tl); break; }
             int *sg = (op.stream == chol::ST_C && !safe) ? ctr[chol::CTR_SIG1] : nullptr;
-            if (op.nst == 16) k_gemm_nt_pipe<0, 16><<<op.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, prio, sg, nullptr, 0, 16, op.tl);
-            else if (op.nst == 32) k_gemm_nt_pipe<0, 32><<<op.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, prio, sg, nullptr, 0, 32, op.tl);
-            else if (tail_of[oi] >= 0) {
+            // (a launch with a tail first, whatever its K: with two panels per super-step the host is a K = 256 update, and the
+            //  compile-time form of that length has no tail -- the product riding in it was skipped above and must not be lost)
+            if (tail_of[oi] >= 0) {
                 const chol::Op &tp = plan.ops[(size_t)tail_of[oi]];
                 k_gemm_nt_pipe_tail<<<op.map_n + tp.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, op.nst, maps + op.map_off, op.map_n, prio, sg, op.tl,
                                                                                   tp.kb, maps + tp.map_off, s.SI + (size_t)tp.dj * si_elems, ldsi, gate_of(tp, false), tp.tl);
             }
+            else if (op.nst == 16) k_gemm_nt_pipe<0, 16><<<op.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, prio, sg, nullptr, 0, 16, op.tl);
+            else if (op.nst == 32) k_gemm_nt_pipe<0, 32><<<op.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, prio, sg, nullptr, 0, 32, op.tl);
             else k_gemm_nt_pipe<0, 0><<<op.map_n, 256, lds_pipe, sq>>>(s.S, s.L, npad, op.kb, maps + op.map_off, prio, sg, nullptr, 0, op.nst, op.tl);
             break;
         }

@@ -288,6 +288,18 @@ CASES = [
     (79, (4, 40, 1, 24, 32, 1, 1, 1, 0, 0, 1)), (16, (4, 40, 1, 24, 32, 1, 1, 1, 0, 0, 1)), (37, (4, 8, 0, 24, 6, 0, 1, 0, 0, 0, 1)),      # the diagonal blocks in ONE resident workgroup (a fifth stream; tools/ only)
 ]
 
+# Every parameter set tests/test_chol_solve_gpu.py runs on the GPU (tests/chol_ref.py: REGIMES at the shipping values, SHRUNK), as the
+# thirteen values of rcn_ba_factor_plan: the block counts at which the shipping plan changes regime, and the same kernels at the
+# smallest shapes with the thresholds shrunk.  tests/test_chol_solve_ref.py checks that the two lists agree.
+SHIPPING = (4, 40, 1, 24, 32, 0, 1, 1, 0, 0, 0, 0, 0)
+GPU_SOLVE_CASES = [
+    (1, SHIPPING), (2, SHIPPING), (3, SHIPPING), (6, SHIPPING), (27, SHIPPING), (34, SHIPPING), (48, SHIPPING),
+    (7, (0, 40, 1, 2, 2, 0, 1, 1, 0, 0, 0, 0, 0)),
+    (12, (2, 4, 1, 2, 2, 0, 1, 1, 0, 0, 0, 0, 0)), (16, (4, 4, 1, 2, 2, 0, 1, 1, 0, 0, 0, 0, 0)),
+    (12, (2, 4, 1, 2, 2, 0, 0, 0, 0, 0, 0, 0, 0)), (16, (4, 4, 1, 2, 2, 0, 0, 0, 0, 0, 0, 0, 0)),
+]
+CASES += GPU_SOLVE_CASES
+
 
 @pytest.mark.parametrize("nblk,params", CASES)
 def test_list_order_is_a_cholesky_factorisation(nblk, params):
@@ -414,3 +426,8 @@ def test_bulk_updates_behind_the_next_diagonal_block():
         assert ops[prev_diag]["kb"] == ops[i]["kb"] + ops[i]["nst"] // 16, "the next diagonal block is listed in front of the bulk update"
         assert not any(ops[j]["stream"] == 0 for j in range(prev_diag + 1, i))
         assert any(c == 0 and v >= ops[prev_diag]["ticket"] - 1 for c, v in ops[i]["waits"])
+
+
+@pytest.mark.parametrize("nblk,params", GPU_SOLVE_CASES)
+def test_the_gpu_solve_cases_in_any_order_the_waits_allow(nblk, params):
+    test_any_order_the_waits_allow_gives_the_same_bits(nblk, params)
