@@ -58,6 +58,12 @@ int rcn_create(int device_id, rcn_ctx **out)
     ctx->coarse_i8_shape = i8s ? (i8s[0] == '1' ? 1 : 0) : -1;
     const char *fe = std::getenv("RCN_FORCE_EXACT");
     ctx->force_exact = fe && fe[0] == '1';
+    const char *mi8 = std::getenv("RCN_MID_I8");
+    ctx->mid_i8_off = mi8 && mi8[0] == '0';
+    const char *rrp = std::getenv("RCN_RERANK_PASS");
+    ctx->rerank_pass = rrp && rrp[0] == '1';
+    const char *flp = std::getenv("RCN_FILTER_PASS");
+    ctx->filter_pass = flp && flp[0] == '1';
     const char *nio = getenv("RCN_MATCH_NO_ORDER");
     ctx->no_item_order = nio && nio[0] == '1';
     const char *ab = std::getenv("RCN_COARSE_ABL");

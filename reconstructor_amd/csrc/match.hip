@@ -822,6 +822,7 @@ struct RerankArgs {
     int64_t out_stride;
     unsigned long long *fb_list;  // (pair << 32 | query) rows needing the exact kernel
     unsigned *fb_count;
+    unsigned *fb_tacc;            // parallel to fb_list: the middle tier's integer threshold (mid_thr_acc; 0 = none) of the rows the RE-RANK appends; NULL: not kept
     unsigned long long *sv_list;  // rows that survive the coarse filter: exact re-rank
     unsigned *sv_count;
     int32_t n_pairs, kq_stride, D, qblocks, pair_base;
@@ -829,7 +830,17 @@ struct RerankArgs {
     float ratio;
     const ScaleDev *sc;  // error model of the coarse pass, in HBM: see rcn_internal.h
     int32_t all_to_fallback;
+    int32_t filter_pass, rerank_pass;   // diagnostic build (RCN_FILTER_PASS / RCN_RERANK_PASS): k_filter certifies nothing / certify's verdict is ignored
 };
+
+// (the shipping library has no such switches: there the flags are compile-time zeros and k_filter / the re-rank keep their code)
+#ifdef RCN_DIAG
+#define RCN_FILTER_PASS(a) ((a).filter_pass != 0)
+#define RCN_RERANK_PASS(a) ((a).rerank_pass != 0)
+#else
+#define RCN_FILTER_PASS(a) false
+#define RCN_RERANK_PASS(a) false
+#endif
 
 // ---- certified decision from exact candidate distances --------------
 // ea<=eb exact (fp64 chain) distances of the two candidates (ia, ib), ordered by (value, idx);
@@ -902,8 +913,23 @@ __device__ __forceinline__ double big_lower_bound(const unsigned long long *bigm
     return d > 0.0 ? d * d * (1.0 - 1e-9) : 0.0;
 }
 
+// Integer threshold of the middle tier (k_mid_eval_i8, mid_i8.h) for a row that leaves the re-rank (0: none, the row keeps the fp32 sweep).
+// eb = the larger of the two candidates' exact distances: an upper bound of the exact SECOND-nearest distance.  With
+//     accof(d2) = BIAS + (s^2 / 2) (d2 - |q|^2)            (the inverse of acc_to_d2)
+// a row t with exact d2(q, t) <= eb has real-valued accumulator A*(t) <= accof(eb) and |acc(t) - A*(t)| <= E(q) (coarse_eps_row), so
+// acc(t) <= accof(eb) + E(q), and acc(t) being an integer, acc(t) <= floor(accof(eb) + E(q)).  One more for the fp64 evaluation of
+// the bound (the slack widens eb the way lbnc's narrows its bound).
+__device__ __forceinline__ unsigned mid_thr_acc(const ScaleDev &S, const ImgDev &qi, int q, double nq2, double eb, unsigned key2, uint32_t mask)
+{
+    if (!S.coarse_i8 || key_is_pad(S, key2, mask) || !(fabs(eb) <= 1.7976931348623157e308)) return 0u;
+    const double d2 = eb * (1.0 + S.rel_slack) + S.rel_slack * (nq2 + S.n_max * S.n_max);
+    const double v = floor(S.bias + S.hs2 * (d2 - nq2) + coarse_eps_row(S, qi, q, nq2)) + 1.0;
+    if (!(v >= 1.0) || v >= (double)RCN_I8_PAD_ACC) return 0u;
+    return (unsigned)v;
+}
+
 __device__ __forceinline__ void list_append(unsigned long long *list, unsigned *count, bool want,
-                                            unsigned long long entry)
+                                            unsigned long long entry, unsigned *side = nullptr, unsigned side_value = 0u)
 {
     const unsigned long long m = __ballot(want);
     if (!m) return;
@@ -912,7 +938,11 @@ __device__ __forceinline__ void list_append(unsigned long long *list, unsigned *
     unsigned base = 0;
     if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(m));
     base = __shfl(base, leader);
-    if (want) list[base + __popcll(m & ((1ull << lane) - 1ull))] = entry;
+    if (want) {
+        const unsigned slot = base + __popcll(m & ((1ull << lane) - 1ull));
+        list[slot] = entry;
+        if (side) side[slot] = side_value;
+    }
 }
 
 // K2a: one thread per (pair, query row): decide from the coarse values alone whenever the
@@ -968,13 +998,13 @@ __global__ __launch_bounds__(RCN_FT) void k_filter(RerankArgs a)
                     double lb0 = fmin(acc_to_d2(S, nq2, lo - eps) - slack, lb_big);
                     const double ub1 = acc_to_d2(S, nq2, hi + eps) + slack;
                     if (lb0 < 0.0) lb0 = 0.0;
-                    surv = ratio_pass(lb0, ub1, a.ratio);
+                    surv = ratio_pass(lb0, ub1, a.ratio) || RCN_FILTER_PASS(a);
                     // certified PASS from the coarse values alone: the best candidate's exact
                     // distance is <= ub0, every other row's is >= lbnc (acc >= trunc(second)).
                     // sqrtf, the fp32 conversion and the product with a positive ratio are monotone,
                     // so the test holding at (ub0, lbnc) holds for the exact pair; ub0 < lbnc makes
                     // the candidate the unique nearest neighbour.  No distance needs recomputing.
-                    if (surv && ti.K > 2) {
+                    if (surv && ti.K > 2 && !RCN_FILTER_PASS(a)) {
                         const double hi0 = key_hi(S, c.x, a.idx_mask);
                         const double lo1 = key_lo(S, c.y, a.idx_mask);
                         const double ub0 = acc_to_d2(S, nq2, hi0 + eps) + slack;
@@ -1013,7 +1043,7 @@ __global__ __launch_bounds__(RCN_FT) void k_filter(RerankArgs a)
         const unsigned long long entry = ((unsigned long long)pair << 32) | (unsigned)(q0 + r * RCN_FT);
         const unsigned long long ms = __ballot(survm >> r & 1u), mf = __ballot(fbm >> r & 1u);
         if (survm >> r & 1u) a.sv_list[bs + __popcll(ms & lt)] = entry;
-        if (fbm >> r & 1u) a.fb_list[bf + __popcll(mf & lt)] = entry;
+        if (fbm >> r & 1u) a.fb_list[bf + __popcll(mf & lt)] = entry;      // (no word of fb_tacc is written for these rows: mid_row_tacc)
         bs += (unsigned)__popcll(ms); bf += (unsigned)__popcll(mf);
     }
 }
@@ -1087,6 +1117,7 @@ __global__ __launch_bounds__(64) void k_rerank_lds(RerankArgs a)
             __syncthreads();
         }
         bool fb = false;
+        unsigned tacc = 0u;
         if (live) {
             // the two candidates ordered by (exact value, index), as the oracle's scan would meet them
             double ea = acc, eb = acc2;
@@ -1096,12 +1127,13 @@ __global__ __launch_bounds__(64) void k_rerank_lds(RerankArgs a)
                 const double nq2 = qi.nrm2[q];
                 const double lbacc = key_lo(S, c.y, a.idx_mask);
                 const double lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps_row(S, qi, q, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
-                res = certify(ea, ia, eb, lbnc, a.ratio);
+                res = RCN_RERANK_PASS(a) ? -2 : certify(ea, ia, eb, lbnc, a.ratio);
+                if (res == -2 && a.fb_tacc) tacc = mid_thr_acc(S, qi, q, nq2, eb, c.y, a.idx_mask);
             }
             if (res >= 0) a.out[(size_t)pair * a.out_stride + q] = res;
             else if (res == -2) fb = true;   // out stays -1 (which is also the certified "no match") until the next tier decides
         }
-        list_append(a.fb_list, a.fb_count, fb, e);
+        list_append(a.fb_list, a.fb_count, fb, e, a.fb_tacc, tacc);
     }
 }
 
@@ -1122,15 +1154,16 @@ __global__ void k_rerank_generic(RerankArgs a)
         double eb = exact_d2<false>(qrow, ti.f32 + (size_t)ib * a.D, a.D);
         if (eb < ea || (eb == ea && ib < ia)) { double te = ea; ea = eb; eb = te; ia = ib; }
         double lbnc = INFINITY;
+        const double nq2 = qi.nrm2[q];
         if (ti.K > 2) {
-            const double nq2 = qi.nrm2[q];
             const double lbacc = key_lo(S, c.y, a.idx_mask);
             lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps_row(S, qi, q, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
         }
-        int res = certify(ea, ia, eb, lbnc, a.ratio);
+        int res = RCN_RERANK_PASS(a) ? -2 : certify(ea, ia, eb, lbnc, a.ratio);
         if (res == -2) {
             unsigned slot = atomicAdd(a.fb_count, 1u);
             a.fb_list[slot] = e;
+            if (a.fb_tacc) a.fb_tacc[slot] = ti.K > 2 && ib != ia ? mid_thr_acc(S, qi, q, nq2, eb, c.y, a.idx_mask) : 0u;
             res = -1;
         }
         a.out[(size_t)pair * a.out_stride + q] = res;
@@ -1306,6 +1339,8 @@ struct MidArgs {
     unsigned *hist, *offs, *cursor, *ibase; // per image slot (+ 1): rows, first sorted row, fill cursor, first work item
     unsigned *n_items;
     const float *thr_in;                   // deferred rows (k_mid_defer): their thresholds, computed while their chunk's candidate table was there
+    const unsigned *tacc_in;               // parallel to fb_list: integer thresholds of the int8 sweep (mid_thr_acc; 0 = none), NULL: no row has one
+    unsigned *tacc;                        // per sorted row: the same.  A row with one belongs to k_mid_eval_i8 (mid_i8.h), every other row to k_mid_eval
     unsigned long long *fb2_list;          // overflowed rows -> K2b
     unsigned *fb2_count;
     int32_t *out;
@@ -1392,6 +1427,19 @@ __device__ __forceinline__ float mid_threshold(const MidArgs &a, const ScaleDev 
     }
     return thr;
 }
+// integer threshold of entry i = (pair, q) of the list (0: none).  Only the re-rank writes fb_tacc; the rows k_filter appended itself -- no
+// coarse pass, a query without an ordinary norm, a padding row as second candidate -- are told by the same test from the chunk's candidate
+// table (a.cand: there for a chunk's own list; the deferred list carries values that went through this function already)
+__device__ __forceinline__ unsigned mid_row_tacc(const MidArgs &a, const ScaleDev &S, unsigned i, int pair, int q)
+{
+    if (!a.tacc_in) return 0u;
+    if (a.cand) {
+        if (a.all_to_fallback) return 0u;
+        const double nq2 = a.imgs[a.pairs[2 * pair]].nrm2[q];
+        if (!(nq2 < S.thr2) || key_is_pad(S, a.cand[(size_t)pair * a.kq_stride + q].y, a.idx_mask)) return 0u;
+    }
+    return a.tacc_in[i];
+}
 __global__ __launch_bounds__(256) void k_mid_scatter(MidArgs a)
 {
     const unsigned n = mid_rows(a);
@@ -1406,7 +1454,9 @@ __global__ __launch_bounds__(256) void k_mid_scatter(MidArgs a)
         if (!live) continue;
         const unsigned pos = a.offs[ts] + rank;
         a.sorted[pos] = e;
-        a.thr[pos] = a.thr_in ? a.thr_in[i] : mid_threshold(a, S, pair, q);
+        const unsigned ta = mid_row_tacc(a, S, i, pair, q);
+        a.tacc[pos] = ta;
+        a.thr[pos] = ta ? 0.f : a.thr_in ? a.thr_in[i] : mid_threshold(a, S, pair, q);      // (a row of the int8 sweep needs no fp32 threshold)
         a.ccount[pos] = 0u;
     }
 }
@@ -1415,7 +1465,7 @@ __global__ __launch_bounds__(256) void k_mid_scatter(MidArgs a)
 // chunk's rows -- with the one thing the tier needs of the chunk's candidate table, the threshold -- join ONE list of the call, as
 // long as it has room (cap rows; a chunk that does not fit goes through the tier at once, as before), and the tier runs once, behind
 // the last chunk, where an image's rows of all chunks share its sweeps.  c = the chunk counters (c[0] rows, c[7] rows deferred so far).
-__global__ __launch_bounds__(256) void k_mid_defer(MidArgs a, unsigned long long *def_e, float *def_thr, const unsigned *c, unsigned cap)
+__global__ __launch_bounds__(256) void k_mid_defer(MidArgs a, unsigned long long *def_e, float *def_thr, unsigned *def_tacc, const unsigned *c, unsigned cap)
 {
     const unsigned n = c[0], base = c[7];
     if (n == 0 || base + n > cap || base + n < base) return;
@@ -1423,7 +1473,9 @@ __global__ __launch_bounds__(256) void k_mid_defer(MidArgs a, unsigned long long
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const unsigned long long e = a.fb_list[i];
         def_e[base + i] = e;
-        def_thr[base + i] = mid_threshold(a, S, (int)(e >> 32), (int)(e & 0xFFFFFFFFu));
+        const unsigned ta = mid_row_tacc(a, S, i, (int)(e >> 32), (int)(e & 0xFFFFFFFFu));
+        def_tacc[base + i] = ta;
+        def_thr[base + i] = ta ? 0.f : mid_threshold(a, S, (int)(e >> 32), (int)(e & 0xFFFFFFFFu));
     }
 }
 // (one thread, behind k_mid_defer: the same test; the rows count as fallback rows of the call and leave the chunk's list)
@@ -1461,7 +1513,7 @@ __device__ __forceinline__ float mid_err(int D, float qn, float tn)
     return ((float)(D + 8) * 2.3841858e-7f * qn * tn + 4.7683716e-7f * tn * tn + (float)(D + 8) * 2.220446e-16f * s * s) * 1.0001f + 1.0e-30f;
 }
 template <int MODE>
-__device__ __forceinline__ void mid_sweep(const MidArgs &a, const ImgDev &ti, const float *const *qptr, int nq, int first, const float *thr, const float *qnorm,
+__device__ __forceinline__ void mid_sweep(const MidArgs &a, const ImgDev &ti, const float *const *qptr, int nq, const unsigned *qslot, const float *thr, const float *qnorm,
                                           int rows, float *tt, float *tq, float (&m1)[RCN_MIDQ], float (&m2)[RCN_MIDQ])
 {
     const int t = threadIdx.x, D = a.D, nchunk = (D + 31) / 32;
@@ -1531,8 +1583,8 @@ __device__ __forceinline__ void mid_sweep(const MidArgs &a, const ImgDev &ti, co
                 const float val = MODE == 0 ? dot : fmaf(-2.f, dot, nt);
                 if (MODE == 0) {
                     if (val <= thr[q]) {
-                        const unsigned pos = atomicAdd(a.ccount + first + q, 1u);
-                        if (pos < (unsigned)RCN_MIDCAP) a.clist[(size_t)(first + q) * RCN_MIDCAP + pos] = j;
+                        const unsigned pos = atomicAdd(a.ccount + qslot[q], 1u);
+                        if (pos < (unsigned)RCN_MIDCAP) a.clist[(size_t)qslot[q] * RCN_MIDCAP + pos] = j;
                     }
                 } else {
                     const float E = mid_err(D, qnorm[q], tn);
@@ -1540,8 +1592,8 @@ __device__ __forceinline__ void mid_sweep(const MidArgs &a, const ImgDev &ti, co
                         // (a NaN value fails the test: such a row is never a neighbour, K2b would not select it either; an infinite
                         //  bound lets everything through, the list overflows and K2b decides)
                         if (val - E <= thr[q]) {
-                            const unsigned pos = atomicAdd(a.ccount + first + q, 1u);
-                            if (pos < (unsigned)RCN_MIDCAP) a.clist[(size_t)(first + q) * RCN_MIDCAP + pos] = j;
+                            const unsigned pos = atomicAdd(a.ccount + qslot[q], 1u);
+                            if (pos < (unsigned)RCN_MIDCAP) a.clist[(size_t)qslot[q] * RCN_MIDCAP + pos] = j;
                         }
                     } else {
                         const float ub = val + E;            // the row's exact value is at most this
@@ -1560,7 +1612,8 @@ __global__ __launch_bounds__(256, 4) void k_mid_eval(MidArgs a)
     __shared__ const float *qptr[RCN_MIDQ];
     __shared__ float thr[RCN_MIDQ], qnorm[RCN_MIDQ];
     __shared__ float red[4][RCN_MIDQ][2];
-    __shared__ int s_need2, s_bin;
+    __shared__ unsigned qslot[RCN_MIDQ];                        // sorted position of the item's own rows (those without an integer threshold)
+    __shared__ int s_need2, s_bin, s_nown;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const unsigned n_items = *a.n_items;
     for (unsigned it = blockIdx.x; it < n_items; it += gridDim.x) {
@@ -1574,22 +1627,31 @@ __global__ __launch_bounds__(256, 4) void k_mid_eval(MidArgs a)
         __syncthreads();
         const int bin = s_bin;
         const unsigned k = it - a.ibase[bin], h = a.offs[bin + 1] - a.offs[bin];
-        const int first = (int)(a.offs[bin] + RCN_MIDQ * k), nq = (int)min((unsigned)RCN_MIDQ, h - RCN_MIDQ * k);
+        const int first = (int)(a.offs[bin] + RCN_MIDQ * k), nall = (int)min((unsigned)RCN_MIDQ, h - RCN_MIDQ * k);
         const ImgDev ti = a.imgs[bin];
-        if (t < nq) {
-            const unsigned long long e = a.sorted[first + t];
-            const int pair = (int)(e >> 32), q = (int)(e & 0xFFFFFFFFu);
-            const ImgDev qi = a.imgs[a.pairs[2 * pair]];
-            qptr[t] = qi.f32 + (size_t)q * a.D;
-            qnorm[t] = (float)(sqrt(qi.nrm2[q]) * (1.0 + 1e-6));
-            const float th = a.thr[first + t];
-            thr[t] = th;
-            if (!(th < INFINITY)) s_need2 = 1;
+        if (t < 64) {                                           // (RCN_MIDQ <= 64: one wave compacts the item's own rows; the others are k_mid_eval_i8's)
+            const bool own = t < nall && a.tacc[first + t] == 0u;
+            const unsigned long long om = __ballot(own);
+            if (t == 0) s_nown = __popcll(om);
+            if (own) {
+                const int o = __popcll(om & ((1ull << t) - 1ull));
+                const unsigned long long e = a.sorted[first + t];
+                const int pair = (int)(e >> 32), q = (int)(e & 0xFFFFFFFFu);
+                const ImgDev qi = a.imgs[a.pairs[2 * pair]];
+                qslot[o] = (unsigned)(first + t);
+                qptr[o] = qi.f32 + (size_t)q * a.D;
+                qnorm[o] = (float)(sqrt(qi.nrm2[q]) * (1.0 + 1e-6));
+                const float th = a.thr[first + t];
+                thr[o] = th;
+                if (!(th < INFINITY)) s_need2 = 1;
+            }
         }
         __syncthreads();
+        const int nq = s_nown;
+        if (nq == 0) continue;                                  // an item without rows of its own
         float m1[RCN_MIDQ], m2[RCN_MIDQ];
         if (!s_need2) {
-            mid_sweep<0>(a, ti, qptr, nq, first, thr, qnorm, ti.K, tt, tq, m1, m2);
+            mid_sweep<0>(a, ti, qptr, nq, qslot, thr, qnorm, ti.K, tt, tq, m1, m2);
             continue;
         }
         // No bound on the second neighbour before the sweep.  ANY two rows give one: the second smallest upper bound over a
@@ -1598,7 +1660,7 @@ __global__ __launch_bounds__(256, 4) void k_mid_eval(MidArgs a)
         const int prefix = min(ti.K, max(512, ti.K / 4));
 #pragma unroll
         for (int q = 0; q < RCN_MIDQ; ++q) { m1[q] = INFINITY; m2[q] = INFINITY; }
-        mid_sweep<1>(a, ti, qptr, nq, first, thr, qnorm, prefix, tt, tq, m1, m2);
+        mid_sweep<1>(a, ti, qptr, nq, qslot, thr, qnorm, prefix, tt, tq, m1, m2);
 #pragma unroll
         for (int q = 0; q < RCN_MIDQ; ++q) {
             float b1 = m1[q], b2 = m2[q];
@@ -1621,9 +1683,10 @@ __global__ __launch_bounds__(256, 4) void k_mid_eval(MidArgs a)
             thr[t] = b2 < INFINITY ? b2 + fabsf(b2) * 1.0e-6f : INFINITY;      // (a NaN bound compares false: INFINITY, K2b decides)
         }
         __syncthreads();
-        mid_sweep<2>(a, ti, qptr, nq, first, thr, qnorm, ti.K, tt, tq, m1, m2);
+        mid_sweep<2>(a, ti, qptr, nq, qslot, thr, qnorm, ti.K, tt, tq, m1, m2);
     }
 }
+#include "mid_i8.h"
 // one wave per row of the tier: the canonical fp64 chain of its candidates, (value, index)-ordered top-2, ratio test
 __global__ __launch_bounds__(256) void k_mid_exact(MidArgs a)
 {
@@ -2385,9 +2448,19 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
     // (the bins come FIRST: their place must not move with the row count of the grid, they carry state -- zeros -- from call to call)
     const size_t mo_bins = 0, mo_sorted = mo_bins + al(4 * 4 * ((size_t)n_slots + 1)), mo_thr = mo_sorted + al(8 * mid_rows_cap), mo_cc = mo_thr + al(4 * mid_rows_cap),
                  mo_cl = mo_cc + al(4 * mid_rows_cap), mo_fb2 = mo_cl + al(4 * mid_rows_cap * RCN_MIDCAP), mo_def = mo_fb2 + al(8 * mid_rows_cap),
-                 mo_defthr = mo_def + (n_chunks > 1 ? al(8 * mid_rows_cap) : 0), mo_end = mo_defthr + (n_chunks > 1 ? al(4 * mid_rows_cap) : 0);
+                 mo_defthr = mo_def + (n_chunks > 1 ? al(8 * mid_rows_cap) : 0), mo_deftacc = mo_defthr + (n_chunks > 1 ? al(4 * mid_rows_cap) : 0),
+                 mo_tacc = mo_deftacc + (n_chunks > 1 ? al(4 * mid_rows_cap) : 0), mo_fbtacc = mo_tacc + al(4 * mid_rows_cap),
+                 mo_end = mo_fbtacc + al(4 * (size_t)std::max<int64_t>(1, cap_rows));
+    // the int8 form of the tier's sweep (k_mid_eval_i8): launched beside k_mid_eval wherever the int8 K1 is; like it, it returns at once unless
+    // fix_scale chose the int8 path.  Its grid: (image slot x tile) x slabs of the bin's rows, the slabs so that a small grid still fills the chip
+    const bool mid_i8 = mid && mfma && ctx->i8_allowed && !ctx->mid_i8_off;
+    const dim3 mid_i8_grid((unsigned)n_slots * MI8_TILES,
+                           (unsigned)std::max<int64_t>(1, std::min<int64_t>(16, (4 * (int64_t)ctx->prop.multiProcessorCount) / std::max<int64_t>(1, (int64_t)n_slots * MI8_TILES))));
     // the call's list of deferred rows (k_mid_defer): as many rows as one pass of the tier takes
     const bool defer = mid && n_chunks > 1 && uniq_lds && kq_max > 0;
+#ifdef RCN_DIAG
+    ctx->diag_mid = {mid ? (size_t)1 : (size_t)0, mo_sorted, mo_tacc, mo_cc, mo_cl, mid_rows_cap};
+#endif
     if (mid) {
         const bool fresh = mo_end > ctx->mid_ws.cap;
         RCN_HIP(ctx->mid_ws.reserve(mo_end));
@@ -2415,6 +2488,8 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
     ra.ratio = ratio;
     ra.sc = ctx->scale_dev.as<ScaleDev>();
     ra.all_to_fallback = mfma ? 0 : 1;
+    ra.filter_pass = ctx->filter_pass ? 1 : 0; ra.rerank_pass = ctx->rerank_pass ? 1 : 0;
+    ra.fb_tacc = mid_i8 ? (unsigned *)(ctx->mid_ws.as<char>() + mo_fbtacc) : nullptr;
 
     // Order of the work items of a coarse launch: every XCD walks its own contiguous range of the chunk's
     // group list, heaviest groups first, so that the last items to start are the short ones (the tail
@@ -2572,15 +2647,15 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
                 char *mw = ctx->mid_ws.as<char>();
                 MidArgs ma;
                 memset(&ma, 0, sizeof(ma));
-                ma.imgs = imgs; ma.pairs = pairs; ma.cand = cand_c; ma.fb_list = ra.fb_list; ma.fb_count = ccnt;
+                ma.imgs = imgs; ma.pairs = pairs; ma.cand = cand_c; ma.fb_list = ra.fb_list; ma.fb_count = ccnt; ma.tacc_in = ra.fb_tacc;
                 if (defer) {
                     // the chunk's rows join the call's list if they fit (then ccnt[0] is 0 and the kernels below find nothing to do)
                     MidArgs md = ma;
                     md.sc = ra.sc; md.kq_stride = kq_stride; md.D = ctx->D; md.all_to_fallback = ra.all_to_fallback; md.idx_mask = idx_mask;
-                    k_mid_defer<<<ctx->prop.multiProcessorCount * 2, 256, 0, st>>>(md, (unsigned long long *)(mw + mo_def), (float *)(mw + mo_defthr), ccnt, (unsigned)mid_rows_cap);
+                    k_mid_defer<<<ctx->prop.multiProcessorCount * 2, 256, 0, st>>>(md, (unsigned long long *)(mw + mo_def), (float *)(mw + mo_defthr), (unsigned *)(mw + mo_deftacc), ccnt, (unsigned)mid_rows_cap);
                     k_mid_defer_commit<<<1, 64, 0, st>>>(ccnt, (unsigned)mid_rows_cap);
                 }
-                ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc);
+                ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc); ma.tacc = (unsigned *)(mw + mo_tacc);
                 ma.clist = (int32_t *)(mw + mo_cl); ma.fb2_list = (unsigned long long *)(mw + mo_fb2);
                 ma.hist = (unsigned *)(mw + mo_bins); ma.offs = ma.hist + (n_slots + 1); ma.cursor = ma.offs + (n_slots + 1); ma.ibase = ma.cursor + (n_slots + 1);
                 ma.n_items = ccnt + 3; ma.fb2_count = ccnt + 2;
@@ -2591,6 +2666,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
                 k_mid_bins<<<1, 1024, 0, st>>>(ma);
                 k_mid_scatter<<<mb, 256, 0, st>>>(ma);
                 k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
+                if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
                 k_mid_exact<<<mb, 256, 0, st>>>(ma);
                 RCN_HIP(hipGetLastError());
                 // K2b: the overflow list, then the rows beyond the tier's budget (none unless a chunk leaves more than RCN_MIDROWS rows)
@@ -2627,7 +2703,8 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
         memset(&ma, 0, sizeof(ma));
         ma.imgs = imgs; ma.pairs = pairs; ma.cand = nullptr; ma.fb_list = (const unsigned long long *)(mw + mo_def); ma.fb_count = ccnt + 7;
         ma.thr_in = (const float *)(mw + mo_defthr);
-        ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc);
+        ma.tacc_in = mid_i8 ? (const unsigned *)(mw + mo_deftacc) : nullptr;
+        ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc); ma.tacc = (unsigned *)(mw + mo_tacc);
         ma.clist = (int32_t *)(mw + mo_cl); ma.fb2_list = (unsigned long long *)(mw + mo_fb2);
         ma.hist = (unsigned *)(mw + mo_bins); ma.offs = ma.hist + (n_slots + 1); ma.cursor = ma.offs + (n_slots + 1); ma.ibase = ma.cursor + (n_slots + 1);
         ma.n_items = ccnt + 3; ma.fb2_count = ccnt + 2;
@@ -2638,6 +2715,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
         k_mid_bins<<<1, 1024, 0, st>>>(ma);
         k_mid_scatter<<<mb, 256, 0, st>>>(ma);
         k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
+        if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
         k_mid_exact<<<mb, 256, 0, st>>>(ma);
         k_exact_rows_lds<<<ctx->prop.multiProcessorCount * 8, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ma.fb2_list, ma.fb2_count, ctx->D, ratio, out_dev, out_stride);
         k_stats_acc_deferred<<<1, 64, 0, st>>>(ccnt);
@@ -2954,6 +3032,34 @@ int rcn_diag_i8(rcn_ctx *ctx, double *model, int32_t img_id, int8_t *q_host, int
         for (int r = 0; r < im.K; ++r)
             for (int c = 0; c < 16; ++c) memcpy(q_host + (size_t)r * 256 + 16 * c, raw.data() + (size_t)r * 256 + ((c ^ (r & 15)) << 4), 16);
     if (norms_host) memcpy(norms_host, nn.data(), nn.size() * sizeof(float));
+    return RCN_OK;
+}
+#endif
+
+#ifdef RCN_DIAG
+// Diagnostic build only: the middle tier's lists as the LAST pass of the last grid call left them (a grid of one pipeline chunk: the
+// only pass).  n_rows: rows the pass took; per row, in binned order (any pointer may be NULL, cap = rows the arrays hold): the entry
+// (pair << 32 | query), the integer threshold of the int8 sweep (0: the fp32 sweep), the number of rows under the threshold and the
+// first RCN_MIDCAP (32) of them.
+int rcn_diag_mid(rcn_ctx *ctx, int64_t *n_rows, unsigned long long *sorted_host, uint32_t *tacc_host, uint32_t *ccount_host, int32_t *clist_host, int64_t cap)
+{
+    if (!ctx || !n_rows) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->diag_mid[0] || !ctx->mid_ws.p || ctx->last_chunks != 1) { ctx->set_error("rcn_diag_mid: the last grid call left no single pass of the middle tier"); return RCN_ERR_UNSUPPORTED; }
+    RCN_HIP(hipSetDevice(ctx->device));
+    unsigned c0 = 0;
+    RCN_HIP(hipMemcpyAsync(&c0, ctx->counters.as<unsigned>() + 8, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t n = std::min<size_t>(c0, ctx->diag_mid[5]);
+    *n_rows = (int64_t)n;
+    if (n == 0 || (!sorted_host && !tacc_host && !ccount_host && !clist_host)) return RCN_OK;
+    if ((int64_t)n > cap) { ctx->set_error("rcn_diag_mid: the arrays are too short"); return RCN_ERR_ARG; }
+    const char *mw = ctx->mid_ws.as<char>();
+    if (sorted_host) RCN_HIP(hipMemcpyAsync(sorted_host, mw + ctx->diag_mid[1], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (tacc_host) RCN_HIP(hipMemcpyAsync(tacc_host, mw + ctx->diag_mid[2], n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (ccount_host) RCN_HIP(hipMemcpyAsync(ccount_host, mw + ctx->diag_mid[3], n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (clist_host) RCN_HIP(hipMemcpyAsync(clist_host, mw + ctx->diag_mid[4], n * 4 * RCN_MIDCAP, hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipStreamSynchronize(ctx->stream));
     return RCN_OK;
 }
 #endif

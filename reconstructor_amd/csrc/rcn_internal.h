@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -204,6 +205,10 @@ struct rcn_ctx {
     int coarse_shape = -1;     // RCN_COARSE_S16=0/1: force k_coarse_top2's MFMA shape (0: 32x32x16, 1: 16x16x32) at every D; -1: the shipping choice
     int ablate = 0;            // RCN_COARSE_ABL
     bool force_exact = false;  // RCN_FORCE_EXACT=1: skip the MFMA coarse pass
+    bool mid_i8_off = false;   // RCN_MID_I8=0: on the int8 path too, every row of the middle tier takes the fp32 sweep (no k_mid_eval_i8)
+    bool rerank_pass = false;  // RCN_RERANK_PASS=1: certify's verdict is ignored, every re-ranked row goes to the middle tier
+    bool filter_pass = false;  // RCN_FILTER_PASS=1: k_filter certifies nothing, every row with a coarse pair goes to the re-rank
+    std::array<size_t, 6> diag_mid{};   // rcn_diag_mid: {the last grid call had a middle tier, offsets of sorted / tacc / ccount / clist in mid_ws, rows they hold}
     bool no_item_order = false;   // RCN_MATCH_NO_ORDER=1: work items in pair order instead of heaviest-first per XCD
     bool ba_atomics = false;   // RCN_BA_SCHUR_ATOMICS=1: atomic Schur accumulation instead of the gather form
     bool ba_trsv_fwd = false;  // RCN_BA_TRSV_FWD=1: separate forward substitution instead of the rhs row inside the factorisation
@@ -214,6 +219,7 @@ struct rcn_ctx {
     static constexpr int coarse_i8_shape = -1;
     static constexpr int coarse_shape = -1;
     static constexpr int ablate = 0;
+    static constexpr bool mid_i8_off = false, rerank_pass = false, filter_pass = false;
     static constexpr bool force_exact = false, no_item_order = false, ba_atomics = false, ba_trsv_fwd = false, ba_pair_small = true;
 #endif
 
