@@ -749,6 +749,68 @@ int rcn_landmark_attach(rcn_ctx *ctx, const double *pose34, const double *intr6,
                         const int32_t *landmark, const int32_t *feat, const int32_t *xy, double max_projection_error,
                         uint8_t *status_out, int32_t *n_attached_out);
 
+/* ---- next view: the candidates of step 3 of triangulateMatchedLandmarks ---------------------------
+ * SequentialReconstructor.cpp:514-553, on the resident match lists and coordinates.
+ *
+ * The landmark-id table is the device copy of features[*][*]->landmarkId: one int32 per keypoint of every image with
+ * resident coordinates, -1 = not a landmark (the only thing the reference ever tests).
+ *   rcn_landmark_ids_reset  sizes the table from the resident coordinates, every entry -1.  RCN_ERR_ARG: no lists, no
+ *                           coordinates.  A later rcn_match_lists_upload / _clear or any change of the coordinates
+ *                           (rcn_coords_upload, _batch, _clear) invalidates the table: every call below then fails with
+ *                           RCN_ERR_ARG and a message until the next reset; nothing stale is read.
+ *   rcn_landmark_ids_set    n host entries (image, feature, id), id -1 frees the entry; a repeated (image, feature) must
+ *                           carry one id.  RCN_ERR_NOT_FOUND: an image without a row; RCN_ERR_ARG: a feature outside the
+ *                           image's keypoints, an id < -1.  Waits for the scatter (the host arrays are borrowed).
+ *   rcn_landmark_ids_read   the K ids of one image (K must be the image's keypoint count).
+ *
+ * rcn_new_view_tracks_device: the tracks the reference's loop would hand to triangulateMultiView for the new image v.
+ *   reg_img_host   the n_reg registered images the caller would visit, in ITS registeredImages iteration order (never
+ *                  sorted here), already filtered to status == true and membership in imgMatches[v]; distinct, without v
+ *   cam_v, reg_cam_host   the camera rows of v and of every registered image in the caller's pose array
+ * For f = 0 .. K_v - 1 with id[v][f] == -1: the smallest k such that featureMatches[(v, reg[k])] maps f -> g and
+ * id[reg[k]][g] == -1 gives the track [(reg[k], g), (v, f)] (the registered observation first); a taken partner does not
+ * end the search.  featureMatches[(v, r)] is the resident list (v, r), under mirror (r, v) read backwards, as in
+ * rcn_corr_2d3d.  Outputs, all in DEVICE memory, in ascending f, rcn_triangulation_problem's layout:
+ *   n_tracks_dev   the number of tracks, also when it exceeds `capacity` (tracks past it are dropped, nothing is written
+ *                  out of bounds)
+ *   trk_off_dev    capacity + 1: trk_off[j] = 2 min(j, n_tracks) -- rows past the count are empty tracks (status 1 of
+ *                  rcn_triangulate_device)
+ *   obs_cam_dev    2 capacity; obs_xy_dev 2 capacity x 2 from the resident coordinates; trk_src_dev capacity x 3 =
+ *                  (reg image id, g, f).  Rows past the count are left as they were.
+ * Asynchronous on the ctx stream after one small staged host-to-device copy (the registered images' table).
+ * RCN_ERR_ARG: no lists, no (or an invalidated) table, a repeated registered image, v among them, capacity > 2^30;
+ * RCN_ERR_NOT_FOUND: an image that is not among the resident lists' images.  A list entry outside its images' keypoints is
+ * ignored on the device. */
+int rcn_landmark_ids_reset(rcn_ctx *ctx);
+int rcn_landmark_ids_set(rcn_ctx *ctx, int32_t n, const int32_t *img, const int32_t *feat, const int32_t *id);
+int rcn_landmark_ids_read(rcn_ctx *ctx, int32_t img, int32_t *out, int32_t K);
+int rcn_new_view_tracks_device(rcn_ctx *ctx, int32_t v, int32_t n_reg, const int32_t *reg_img_host, int32_t cam_v,
+                               const int32_t *reg_cam_host, int32_t capacity, int32_t *n_tracks_dev, int32_t *trk_off_dev,
+                               int32_t *obs_cam_dev, int32_t *obs_xy_dev, int32_t *trk_src_dev);
+/* rcn_new_view_tracks_device, then rcn_triangulate_device over the `capacity` rows with the caller's poses34_dev /
+ * intrinsics_dev (n_cams rows, DEVICE memory; out_xyz_dev capacity x 3, out_status_dev capacity bytes, out_compact_dev /
+ * compact_first / out_n_accepted_dev as there), then the commit: accepted track j gets landmark id first_landmark + (the
+ * number of accepted tracks before j), written into the table for both of its features.  No host synchronisation between
+ * the stages.  RCN_ERR_ARG also for a camera row outside 0 .. n_cams - 1. */
+int rcn_new_view_triangulate_device(rcn_ctx *ctx, int32_t v, int32_t n_reg, const int32_t *reg_img_host, int32_t cam_v,
+                                    const int32_t *reg_cam_host, int32_t n_cams, const double *poses34_dev, const double *intrinsics_dev,
+                                    double max_projection_error, double min_triangulation_angle, int32_t first_landmark, int32_t capacity,
+                                    int32_t *n_tracks_dev, int32_t *trk_off_dev, int32_t *obs_cam_dev, int32_t *obs_xy_dev,
+                                    int32_t *trk_src_dev, double *out_xyz_dev, uint8_t *out_status_dev, double *out_compact_dev,
+                                    int32_t compact_first, int32_t *out_n_accepted_dev);
+/* Step 3 for the new view v straight into the session: rcn_new_view_triangulate_device with one row per keypoint of v,
+ * camera rows = session indices, poses34_host as in rcn_ba_session_validity, the intrinsics the session's own.  Bit for bit
+ * the candidates of the host walk flattened and handed to rcn_ba_session_triangulate: the same points, the same graph in
+ * the same order, the same statuses.  The table is committed with the session's landmark indices.  One copy comes back:
+ * per candidate (reg image, g, f), both pixels (the host mirror of the graph stores them) and the status byte.
+ * n_tracks_out, trk_src_out (room for K_v x 3), status_out (room for K_v bytes), first_index_out, n_added_out may be NULL.
+ * rcn_ba_session_attach and rcn_ba_session_remove_outliers do not touch the table: keep it current with
+ * rcn_landmark_ids_set. */
+int rcn_ba_session_grow_view(rcn_ba_session *s, const double *poses34_host, int32_t v, int32_t cam_v, int32_t n_reg,
+                             const int32_t *reg_img, const int32_t *reg_cam, double max_projection_error,
+                             double min_triangulation_angle, int32_t *n_tracks_out, int32_t *trk_src_out, uint8_t *status_out,
+                             int32_t *first_index_out, int32_t *n_added_out);
+
 /* ---- view registration: P3P-RANSAC + refit ----------------------------------------------------
  * SequentialReconstructor::registerImagePnP (SequentialReconstructor.cpp:559-638) for a batch of views: cv::solvePnPRansac
  * in its P3P mode (4-entry samples from cv::RNG, closed-form 3-point solver, the fourth entry picks the solution; squared

@@ -35,6 +35,8 @@ SYMBOLS = [
     "rcn_triangulate", "rcn_triangulate_device",
     "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
     "rcn_landmark_attach", "rcn_ba_session_attach",
+    "rcn_landmark_ids_reset", "rcn_landmark_ids_set", "rcn_landmark_ids_read", "rcn_new_view_tracks_device",
+    "rcn_new_view_triangulate_device", "rcn_ba_session_grow_view",
     "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
     "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
     "rcn_kp_detect_device", "rcn_kp_nms_device",
@@ -419,6 +421,20 @@ def load():
     L.rcn_landmark_attach.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
     L.rcn_ba_session_attach.restype = C.c_int
     L.rcn_ba_session_attach.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_double, vp, C.POINTER(i32)]
+    L.rcn_landmark_ids_reset.restype = C.c_int
+    L.rcn_landmark_ids_reset.argtypes = [vp]
+    L.rcn_landmark_ids_set.restype = C.c_int
+    L.rcn_landmark_ids_set.argtypes = [vp, i32, vp, vp, vp]
+    L.rcn_landmark_ids_read.restype = C.c_int
+    L.rcn_landmark_ids_read.argtypes = [vp, i32, vp, i32]
+    L.rcn_new_view_tracks_device.restype = C.c_int
+    L.rcn_new_view_tracks_device.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.rcn_new_view_triangulate_device.restype = C.c_int
+    L.rcn_new_view_triangulate_device.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.c_double, C.c_double, i32, i32,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.rcn_ba_session_grow_view.restype = C.c_int
+    L.rcn_ba_session_grow_view.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.c_double, C.c_double, C.POINTER(i32), vp, vp,
+                                           C.POINTER(i32), C.POINTER(i32)]
     L.rcn_pnp_default_options.restype = None
     L.rcn_pnp_default_options.argtypes = [C.POINTER(PnpOptions)]
     L.rcn_pnp_ransac.restype = C.c_int

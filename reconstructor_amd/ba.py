@@ -245,6 +245,29 @@ class BaSession:
                                                           float(max_err), st.ctypes.data, C.byref(added)))
         return st[:n], added.value
 
+    def grow_view(self, img, n_keypoints, registered, img_matches, cam_index, poses34=None, max_err=4.0, min_angle=1.0):
+        """Step 3 of triangulateMatchedLandmarks for the new image `img` (n_keypoints features) on the device
+        (rcn_ba_session_grow_view): the candidates from the resident lists and the landmark-id table (newview.LandmarkIds),
+        triangulated straight into the session, the table committed with the new landmarks' indices.  registered /
+        img_matches as triangulate.new_view_tracks takes them (filtered here), cam_index {image: session camera}.  Returns
+        (trk_src[n_tracks, 3] = (reg image, its feature, feature of img), status per candidate, index of the first new
+        landmark, landmarks added) -- what new_view_tracks -> tracks_to_arrays -> triangulate() gives on the same state."""
+        from . import newview
+        if poses34 is None:
+            poses34 = poses34_from_angle_axis(self.cameras()[0])
+        p = np.ascontiguousarray(poses34, np.float64)
+        reg = np.asarray(newview.visited(img, registered, img_matches), np.int32)
+        cam = np.asarray([cam_index[r] for r in reg], np.int32)
+        K = int(n_keypoints)
+        newview.LandmarkIds(self.ctx).read(img, K)          # raises unless img has exactly K keypoints: the arrays below have room
+        src, st = np.zeros((max(K, 1), 3), np.int32), np.zeros(max(K, 1), np.uint8)
+        n, first, added = C.c_int32(), C.c_int32(), C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_grow_view(self.h, p.ctypes.data, int(img), int(cam_index[img]), len(reg),
+                                                             reg.ctypes.data if len(reg) else None, cam.ctypes.data if len(reg) else None,
+                                                             float(max_err), float(min_angle), C.byref(n), src.ctypes.data, st.ctypes.data,
+                                                             C.byref(first), C.byref(added)))
+        return src[:n.value], st[:n.value], first.value, added.value
+
     def pnp(self, landmark, xy, intr6, options=None):
         """registerImagePnP of one view against the session's landmarks in HBM (rcn_ba_session_pnp): entries (landmark,
         integer pixel) in list order.  Returns (pose34[12], inlier mask, count); count < 0: no pose (pnp.pnp_ransac)."""

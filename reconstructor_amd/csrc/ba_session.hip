@@ -20,6 +20,7 @@
 #include <climits>
 #include <atomic>
 #include <cmath>
+#include <unordered_map>
 
 namespace {
 
@@ -70,6 +71,8 @@ struct rcn_ba_session {
     KeepBuf pts;                                     // n_points x 3 doubles, HBM
     DevBuf uv, ocam, opt, xy, pt_off, poses34, intr_dev, inl, keep, cnt, idx, tmp_pts;
     DevBuf t_in, t_xyz, t_ws;                        // rcn_ba_session_triangulate: tracks staged in HBM, every track's X, workspace
+    DevBuf g_in;                                     // rcn_ba_session_grow_view: the candidates' CSR arrays and what comes back to the host
+    std::vector<char> g_host;                        // ... and its host side
     std::vector<int32_t> h_cam, h_pt;                // flattened graph (host), rebuilt with the device arrays
     std::vector<double> h_uv;
     bool obs_dirty = true;                           // device observation arrays do not reflect `tracks`
@@ -145,7 +148,7 @@ void rcn_ba_session_destroy(rcn_ba_session *s)
         if ((ctx->ba_pair_token >> 32) == s->id) ctx->ba_pair_token = 0;
         s->pts.release();
         DevBuf *bufs[] = {&s->uv, &s->ocam, &s->opt, &s->xy, &s->pt_off, &s->poses34, &s->intr_dev, &s->inl, &s->keep, &s->cnt, &s->idx, &s->tmp_pts,
-                          &s->t_in, &s->t_xyz, &s->t_ws};
+                          &s->t_in, &s->t_xyz, &s->t_ws, &s->g_in};
         for (DevBuf *b : bufs) b->release();
     }
     delete s;
@@ -478,6 +481,87 @@ int rcn_ba_session_attach(rcn_ba_session *s, const double *poses34_host, int32_t
     if (added) { s->obs_dirty = true; s->have_inlier = false; ++s->version; }
     if (status_out) std::copy(status.begin(), status.end(), status_out);
     if (n_added_out) *n_added_out = added;
+    return RCN_OK;
+}
+
+// step 3 of triangulateMatchedLandmarks (:514-553) for the new view v, end to end on the device (corr2d3d.hip, triangulate.hip): the
+// candidates from the resident lists and the landmark-id table, the triangulation over one row per keypoint of v (rows past the
+// candidates are empty tracks), the accepted X compacted behind the session's landmarks, their indices committed to the table.  No
+// host synchronisation between the stages; one copy back (count, (reg image, g, f), both pixels and the status per candidate), from
+// which the host mirror of the graph is appended exactly as rcn_ba_session_triangulate appends it.
+int rcn_ba_session_grow_view(rcn_ba_session *s, const double *poses34_host, int32_t v, int32_t cam_v, int32_t n_reg, const int32_t *reg_img,
+                             const int32_t *reg_cam, double max_projection_error, double min_triangulation_angle, int32_t *n_tracks_out,
+                             int32_t *trk_src_out, uint8_t *status_out, int32_t *first_index_out, int32_t *n_added_out)
+{
+    if (!s || !poses34_host || n_reg < 0 || (n_reg > 0 && (!reg_img || !reg_cam))) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    const char *who = "rcn_ba_session_grow_view";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (first_index_out) *first_index_out = np;
+    if (n_added_out) *n_added_out = 0;
+    if (n_tracks_out) *n_tracks_out = 0;
+    if (cam_v < 0 || cam_v >= nc) { ctx->set_error(std::string(who) + ": camera index out of range"); return RCN_ERR_ARG; }
+    std::unordered_map<int32_t, int32_t> cam_of;
+    for (int32_t k = 0; k < n_reg; ++k) {
+        if (reg_cam[k] < 0 || reg_cam[k] >= nc) { ctx->set_error(std::string(who) + ": camera index out of range"); return RCN_ERR_ARG; }
+        cam_of[reg_img[k]] = reg_cam[k];
+    }
+    const int32_t cap = rcn_int_coords_rows(ctx, v);        // one row per keypoint of v: every candidate fits
+    if (cap < 0) { ctx->set_error(std::string(who) + ": image " + std::to_string(v) + " has no coordinates (rcn_coords_upload)"); return RCN_ERR_NOT_FOUND; }
+    if ((int64_t)np + cap > INT32_MAX) { ctx->set_error(std::string(who) + ": too many landmarks"); return RCN_ERR_ARG; }
+    SES_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t nt = (size_t)cap;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    // what comes back, contiguous: n_tracks, n_added, 2 words of padding | trk_src 3 nt | obs_xy 4 nt | status nt bytes
+    const size_t o_src = 16, o_xy = o_src + 12 * nt, o_st = o_xy + 16 * nt, b_back = o_st + nt;
+    const size_t o_off = al(b_back), o_cam = o_off + al(4 * (nt + 1));
+    SES_HIP(s->poses34.reserve(std::max(nc, 1) * 12 * sizeof(double)));
+    SES_HIP(s->intr_dev.reserve(std::max(nc, 1) * 6 * sizeof(double)));
+    SES_HIP(s->g_in.reserve(o_cam + al(8 * std::max<size_t>(nt, 1))));
+    SES_HIP(s->t_xyz.reserve(24 * std::max<size_t>(nt, 1)));
+    SES_HIP(s->t_ws.reserve(rcn_int_triangulate_ws_bytes(nc, cap)));
+    SES_HIP(s->pts.grow(((size_t)np + nt) * 24, (size_t)np * 24, st));          // room for every row behind the landmarks
+    char *g = s->g_in.as<char>();
+    int32_t *d_hdr = reinterpret_cast<int32_t *>(g), *d_src = reinterpret_cast<int32_t *>(g + o_src), *d_xy = reinterpret_cast<int32_t *>(g + o_xy);
+    uint8_t *d_st = reinterpret_cast<uint8_t *>(g + o_st);
+    int32_t *d_off = reinterpret_cast<int32_t *>(g + o_off), *d_cam = reinterpret_cast<int32_t *>(g + o_cam);
+    SES_HIP(hipMemsetAsync(d_hdr, 0, 16, st));
+    SES_HIP(hipMemcpyAsync(s->poses34.p, poses34_host, (size_t)nc * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+    SES_HIP(hipMemcpyAsync(s->intr_dev.p, s->intr.data(), (size_t)nc * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    int rc = rcn_int_new_view_tracks(ctx, who, v, n_reg, reg_img, cam_v, reg_cam, cap, d_hdr, d_off, d_cam, d_xy, d_src);
+    if (rc) return rc;
+    rcn_triangulation_problem dp{nc, cap, 2 * cap, 0, s->poses34.as<double>(), s->intr_dev.as<double>(), d_off, d_cam, d_xy};
+    rc = rcn_int_triangulate_launch(ctx, &dp, max_projection_error, min_triangulation_angle, s->t_ws.p, s->t_xyz.as<double>(), d_st,
+                                    static_cast<double *>(s->pts.p), np, d_hdr + 1);
+    if (rc) return rc;
+    rc = rcn_int_new_view_commit(ctx, v, cap, d_hdr, d_src, d_st, np);
+    if (rc) return rc;
+    s->g_host.resize(b_back);
+    SES_HIP(hipMemcpyAsync(s->g_host.data(), g, b_back, hipMemcpyDeviceToHost, st));
+    SES_HIP(hipStreamSynchronize(st));
+    const int32_t *h_hdr = reinterpret_cast<const int32_t *>(s->g_host.data()), *h_src = reinterpret_cast<const int32_t *>(s->g_host.data() + o_src),
+                  *h_xy = reinterpret_cast<const int32_t *>(s->g_host.data() + o_xy);
+    const uint8_t *h_st = reinterpret_cast<const uint8_t *>(s->g_host.data() + o_st);
+    const int32_t n_tracks = h_hdr[0], added = h_hdr[1];
+    if (n_tracks < 0 || n_tracks > cap) { ctx->set_error(std::string(who) + ": candidate count out of range"); return RCN_ERR_HIP; }
+    int32_t n_acc = 0;
+    for (int32_t j = 0; j < n_tracks; ++j) {
+        if (h_st[j] != 0) continue;
+        std::vector<TrackObs> t;                     // the registered observation first, as the candidates list it
+        t.push_back(TrackObs{cam_of[h_src[3 * (size_t)j]], h_xy[4 * (size_t)j], h_xy[4 * (size_t)j + 1]});
+        t.push_back(TrackObs{cam_v, h_xy[4 * (size_t)j + 2], h_xy[4 * (size_t)j + 3]});
+        s->n_obs += 2;
+        s->tracks.push_back(std::move(t));
+        ++n_acc;
+    }
+    if (n_acc != added) { ctx->set_error(std::string(who) + ": accepted count differs from the status bytes"); return RCN_ERR_HIP; }
+    if (n_acc) { s->obs_dirty = true; s->have_inlier = false; ++s->version; }
+    if (n_tracks_out) *n_tracks_out = n_tracks;
+    if (trk_src_out) std::copy(h_src, h_src + 3 * (size_t)n_tracks, trk_src_out);
+    if (status_out) std::copy(h_st, h_st + n_tracks, status_out);
+    if (n_added_out) *n_added_out = n_acc;
     return RCN_OK;
 }
 

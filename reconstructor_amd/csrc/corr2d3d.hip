@@ -23,6 +23,18 @@
 // Step 1 of triangulateMatchedLandmarks (:497-512), k_attach_rules / k_attach_taken: per entry (fp64, contraction off,
 // camgeom.h reproj_l1) depth > 0, L1 error < max, then the first PASSING entry of every feature wins -- the smallest
 // entry index by atomicMin, which is order-independent.
+//
+// Step 3 of triangulateMatchedLandmarks (:514-553) behind rcn_landmark_ids_* and rcn_new_view_tracks_device (DESIGN.md section
+// 25): for every free feature f of the new image v the FIRST registered image reg[k], in the caller's order, whose list
+// (v, reg[k]) maps f -> g with g free.  A list holds at most one g per f, so that is the minimum of (k, g) over the passing
+// entries of all lists:
+//   N1 k_nvt_walk      one workgroup per registered image: its list, entries with both ends free (landmark id -1 in the
+//                      resident table) do a 64-bit atomicMin of (k << 32) | g into best[f] -- integer min, one value per
+//                      (k, f): the result does not depend on arrival order
+//   N2 k_nvt_emit      one workgroup: ordered compaction of best over f (wg_rank per 1024 features, a running count), both
+//                      pixels gathered, the CSR arrays and (reg image, g, f) per track written in ascending f
+//   N3 k_nvt_commit    behind the triangulation: accepted track j gets landmark first + (accepted tracks before it), written
+//                      into the table for both of its features (ordered rank again; no atomic decides a position)
 #include "camgeom.h"
 #include "wgprim.h"
 
@@ -472,6 +484,310 @@ int rcn_int_pair_fill(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int3
     return RCN_OK;
 }
 
+// ---- step 3 of triangulateMatchedLandmarks: the new view's candidate tracks -------------------------------------------------
+namespace {
+
+constexpr int NB = 1024;                                 // threads of the one workgroup of N2 / N3 (16 waves)
+constexpr unsigned long long NO_BEST = ~0ull;            // best[f]: no list has a free partner for f
+
+struct RegDev { int32_t slot, cam, img, pad; };          // registered image k: its list slot, camera row, image id
+
+__global__ __launch_bounds__(CB) void k_nvt_walk(const RegDev *__restrict__ reg, int32_t sv, const int2 *__restrict__ ent,
+                                                 const int64_t *__restrict__ list_off, const int32_t *__restrict__ dir, int32_t n_slots,
+                                                 const SlotDev *__restrict__ slots, const int32_t *__restrict__ lid,
+                                                 const int64_t *__restrict__ lid_off, unsigned long long *__restrict__ best)
+{
+    const int k = blockIdx.x, sr = reg[k].slot;
+    const int d = dir[(size_t)sv * n_slots + sr];        // featureMatches[(v, reg[k])]
+    if (d < 0) return;                                   // uniform over the workgroup
+    const bool back = d & 1;
+    const int64_t e0 = list_off[d >> 1], e1 = list_off[(d >> 1) + 1];
+    const int Kv = slots[sv].K, Kr = slots[sr].K;
+    const int32_t *idv = lid + lid_off[sv], *idr = lid + lid_off[sr];
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += CB) {
+        const int2 m = ent[e];
+        const int f = back ? m.y : m.x, g = back ? m.x : m.y;
+        if (f < 0 || f >= Kv || g < 0 || g >= Kr) continue;
+        if (idv[f] != -1 || idr[g] != -1) continue;      // :519 and :541: a taken partner does not end the search
+        atomicMin(best + f, ((unsigned long long)(unsigned)k << 32) | (unsigned)g);
+    }
+}
+
+__global__ __launch_bounds__(NB) void k_nvt_emit(const RegDev *__restrict__ reg, int32_t sv, int32_t cam_v,
+                                                 const SlotDev *__restrict__ slots, const unsigned long long *__restrict__ best,
+                                                 int32_t capacity, int32_t *__restrict__ n_tracks, int32_t *__restrict__ trk_off,
+                                                 int32_t *__restrict__ obs_cam, int32_t *__restrict__ obs_xy, int32_t *__restrict__ trk_src)
+{
+    __shared__ int wtot[NB / 64];
+    const int t = threadIdx.x;
+    const SlotDev s = slots[sv];
+    int run = 0;                                         // tracks of the features before this chunk (uniform)
+    for (int f0 = 0; f0 < s.K; f0 += NB) {
+        const int f = f0 + t;
+        const unsigned long long b = f < s.K ? best[f] : NO_BEST;
+        int chunk;
+        const int pos = run + wg_rank<NB>(b != NO_BEST, wtot, chunk);
+        if (b != NO_BEST && pos < capacity) {
+            const RegDev r = reg[(int)(b >> 32)];
+            const int g = (int)(unsigned)b;
+            const int32_t *rxy = slots[r.slot].xy;
+            const size_t p = (size_t)pos;
+            obs_cam[2 * p] = r.cam; obs_cam[2 * p + 1] = cam_v;          // the registered observation first (matchedImgIdFeatId, :543-544)
+            obs_xy[4 * p] = rxy[2 * (size_t)g]; obs_xy[4 * p + 1] = rxy[2 * (size_t)g + 1];
+            obs_xy[4 * p + 2] = s.xy[2 * (size_t)f]; obs_xy[4 * p + 3] = s.xy[2 * (size_t)f + 1];
+            trk_src[3 * p] = r.img; trk_src[3 * p + 1] = g; trk_src[3 * p + 2] = f;
+        }
+        run += chunk;
+    }
+    for (int j = t; j <= capacity; j += NB) trk_off[j] = 2 * min(j, run);
+    if (t == 0) *n_tracks = run;
+}
+
+__global__ __launch_bounds__(NB) void k_nvt_commit(const int32_t *__restrict__ n_tracks, int32_t capacity, const int32_t *__restrict__ trk_src,
+                                                   const uint8_t *__restrict__ status, int32_t sv, const int32_t *__restrict__ id2slot,
+                                                   int32_t id_lo, int32_t id_span, int32_t *__restrict__ lid, const int64_t *__restrict__ lid_off,
+                                                   int32_t first)
+{
+    __shared__ int wtot[NB / 64];
+    const int t = threadIdx.x, n = min(*n_tracks, capacity);
+    int run = 0;
+    for (int j0 = 0; j0 < n; j0 += NB) {
+        const int j = j0 + t;
+        const bool acc = j < n && status[j] == 0;
+        int chunk;
+        const int id = first + run + wg_rank<NB>(acc, wtot, chunk);
+        if (acc) {
+            const int64_t r = (int64_t)trk_src[3 * (size_t)j] - id_lo;
+            const int sr = r >= 0 && r < id_span ? id2slot[r] : -1;
+            lid[lid_off[sv] + trk_src[3 * (size_t)j + 2]] = id;          // distinct tracks have distinct f, and per list distinct g
+            if (sr >= 0) lid[lid_off[sr] + trk_src[3 * (size_t)j + 1]] = id;
+        }
+        run += chunk;
+    }
+}
+
+__global__ void k_lid_scatter(const int64_t *__restrict__ at, const int32_t *__restrict__ id, int32_t n, int32_t *__restrict__ lid)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) lid[at[e]] = id[e];
+}
+
+// the landmark-id table as the current lists and coordinates need it, or an error
+int lid_check(rcn_ctx *ctx, const char *who)
+{
+    if (!ctx->lid_live) { ctx->set_error(std::string(who) + ": no landmark-id table (rcn_landmark_ids_reset)"); return RCN_ERR_ARG; }
+    if (ctx->lid_lists_gen != ctx->lists_gen || ctx->lid_coords_gen != ctx->coords_gen) {
+        ctx->set_error(std::string(who) + ": the landmark-id table was invalidated by a change of the match lists or the coordinates (rcn_landmark_ids_reset)");
+        return RCN_ERR_ARG;
+    }
+    return RCN_OK;
+}
+
+int slot_of(const CorrLists &L, int32_t id)
+{
+    auto it = std::lower_bound(L.ids.begin(), L.ids.end(), id);
+    return it == L.ids.end() || *it != id ? -1 : (int)(it - L.ids.begin());
+}
+
+}  // namespace
+
+int32_t rcn_int_coords_rows(rcn_ctx *ctx, int32_t img)
+{
+    auto it = ctx->coords.find(img);
+    return it == ctx->coords.end() ? -1 : it->second.second;
+}
+
+int rcn_int_new_view_tracks(rcn_ctx *ctx, const char *who, int32_t v, int32_t n_reg, const int32_t *reg_img, int32_t cam_v,
+                            const int32_t *reg_cam, int32_t capacity, int32_t *n_tracks_dev, int32_t *trk_off_dev,
+                            int32_t *obs_cam_dev, int32_t *obs_xy_dev, int32_t *trk_src_dev)
+{
+    CorrLists &L = ctx->corr;
+    if (n_reg < 0 || capacity < 0 || capacity > (1 << 30) || (n_reg > 0 && (!reg_img || !reg_cam)) || !n_tracks_dev || !trk_off_dev ||
+        (capacity > 0 && (!obs_cam_dev || !obs_xy_dev || !trk_src_dev))) {
+        ctx->set_error(std::string(who) + ": bad argument");
+        return RCN_ERR_ARG;
+    }
+    if (!L.live) { ctx->set_error(std::string(who) + ": no match lists (rcn_match_lists_upload)"); return RCN_ERR_ARG; }
+    int rc = lid_check(ctx, who);
+    if (rc) return rc;
+    const int sv = slot_of(L, v);
+    if (sv < 0) { ctx->set_error(std::string(who) + ": image " + std::to_string(v) + " is not among the resident lists' images"); return RCN_ERR_NOT_FOUND; }
+    if (ctx->nvt_stage_pending) { RCN_HIP(hipEventSynchronize(ctx->nvt_ev)); ctx->nvt_stage_pending = false; }     // the staging buffer is free again
+    ctx->nvt_stage_host.resize((size_t)std::max(n_reg, 1) * sizeof(RegDev));
+    RegDev *rd = reinterpret_cast<RegDev *>(ctx->nvt_stage_host.data());
+    std::vector<uint8_t> seen(L.ids.size(), 0);
+    for (int32_t k = 0; k < n_reg; ++k) {
+        const int sr = slot_of(L, reg_img[k]);
+        if (sr < 0) { ctx->set_error(std::string(who) + ": image " + std::to_string(reg_img[k]) + " is not among the resident lists' images"); return RCN_ERR_NOT_FOUND; }
+        if (sr == sv) { ctx->set_error(std::string(who) + ": the new image " + std::to_string(v) + " is among the registered images"); return RCN_ERR_ARG; }
+        if (seen[sr]) { ctx->set_error(std::string(who) + ": registered image " + std::to_string(reg_img[k]) + " is listed twice"); return RCN_ERR_ARG; }
+        seen[sr] = 1;
+        rd[k] = RegDev{sr, reg_cam[k], reg_img[k], 0};
+    }
+    int64_t sum_k = 0;
+    rc = refresh_slots(ctx, who, &sum_k);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    if (!ctx->nvt_ev && hipEventCreateWithFlags(&ctx->nvt_ev, hipEventDisableTiming) != hipSuccess) { ctx->nvt_ev = nullptr; RCN_HIP(hipGetLastError()); }
+    const int32_t Kv = ctx->coords.find(v)->second.second;               // refresh_slots found it
+    const size_t b_reg = al256((size_t)std::max(n_reg, 1) * sizeof(RegDev)), b_best = al256(8 * (size_t)std::max(Kv, 1));
+    RCN_HIP(ctx->nvt_ws.reserve(b_reg + b_best));
+    RegDev *d_reg = ctx->nvt_ws.as<RegDev>();
+    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(ctx->nvt_ws.as<char>() + b_reg);
+    if (n_reg) {
+        RCN_HIP(hipMemcpyAsync(d_reg, rd, (size_t)n_reg * sizeof(RegDev), hipMemcpyHostToDevice, st));
+        RCN_HIP(hipEventRecord(ctx->nvt_ev, st));
+        ctx->nvt_stage_pending = true;
+    }
+    RCN_HIP(hipMemsetAsync(d_best, 0xFF, b_best, st));
+    const SlotDev *slots = ctx->corr_slots.as<SlotDev>();
+    if (n_reg)
+        k_nvt_walk<<<(unsigned)n_reg, CB, 0, st>>>(d_reg, sv, L.ent.as<int2>(), L.list_off.as<int64_t>(), L.dir.as<int32_t>(), (int32_t)L.ids.size(),
+                                                   slots, ctx->lid.as<int32_t>(), ctx->lid_slot_off.as<int64_t>(), d_best);
+    k_nvt_emit<<<1, NB, 0, st>>>(d_reg, sv, cam_v, slots, d_best, capacity, n_tracks_dev, trk_off_dev, obs_cam_dev, obs_xy_dev, trk_src_dev);
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
+
+int rcn_int_new_view_commit(rcn_ctx *ctx, int32_t v, int32_t capacity, const int32_t *n_tracks_dev, const int32_t *trk_src_dev,
+                            const uint8_t *status_dev, int32_t first_landmark)
+{
+    CorrLists &L = ctx->corr;
+    if (capacity == 0) return RCN_OK;
+    k_nvt_commit<<<1, NB, 0, ctx->stream>>>(n_tracks_dev, capacity, trk_src_dev, status_dev, slot_of(L, v), L.id2slot.as<int32_t>(), L.id_lo,
+                                            L.id_span, ctx->lid.as<int32_t>(), ctx->lid_slot_off.as<int64_t>(), first_landmark);
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
+
+extern "C" {
+
+int rcn_landmark_ids_reset(rcn_ctx *ctx)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    const char *who = "rcn_landmark_ids_reset";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CorrLists &L = ctx->corr;
+    ctx->lid_live = false;
+    if (!L.live) { ctx->set_error(std::string(who) + ": no match lists (rcn_match_lists_upload)"); return RCN_ERR_ARG; }
+    if (ctx->coords.empty()) { ctx->set_error(std::string(who) + ": no coordinates (rcn_coords_upload)"); return RCN_ERR_ARG; }
+    ctx->lid_rows.clear();
+    int64_t total = 0;
+    for (auto &kv : ctx->coords) {
+        ctx->lid_rows[kv.first] = std::make_pair(total, kv.second.second);
+        total += kv.second.second;
+    }
+    std::vector<int64_t> so(std::max<size_t>(L.ids.size(), 1), 0);
+    for (size_t s = 0; s < L.ids.size(); ++s) {
+        auto it = ctx->lid_rows.find(L.ids[s]);
+        if (it == ctx->lid_rows.end()) { ctx->set_error(std::string(who) + ": coordinates of image " + std::to_string(L.ids[s]) + " are no longer resident"); return RCN_ERR_ARG; }
+        so[s] = it->second.first;
+    }
+    RCN_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    RCN_HIP(hipStreamSynchronize(st));                   // nothing queued reads the old table any more
+    RCN_HIP(ctx->lid.reserve(4 * (size_t)std::max<int64_t>(total, 1)));
+    RCN_HIP(ctx->lid_slot_off.reserve(8 * so.size()));
+    RCN_HIP(hipMemsetAsync(ctx->lid.p, 0xFF, 4 * (size_t)std::max<int64_t>(total, 1), st));
+    RCN_HIP(hipMemcpyAsync(ctx->lid_slot_off.p, so.data(), 8 * so.size(), hipMemcpyHostToDevice, st));
+    RCN_HIP(hipStreamSynchronize(st));                   // so is a local
+    ctx->lid_lists_gen = ctx->lists_gen;
+    ctx->lid_coords_gen = ctx->coords_gen;
+    ctx->lid_live = true;
+    return RCN_OK;
+}
+
+int rcn_landmark_ids_set(rcn_ctx *ctx, int32_t n, const int32_t *img, const int32_t *feat, const int32_t *id)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    const char *who = "rcn_landmark_ids_set";
+    if (n < 0 || (n > 0 && (!img || !feat || !id))) { ctx->set_error(std::string(who) + ": bad argument"); return RCN_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = lid_check(ctx, who);
+    if (rc) return rc;
+    if (n == 0) return RCN_OK;
+    std::vector<int64_t> at((size_t)n);
+    for (int32_t e = 0; e < n; ++e) {
+        auto it = ctx->lid_rows.find(img[e]);
+        if (it == ctx->lid_rows.end()) { ctx->set_error(std::string(who) + ": image " + std::to_string(img[e]) + " has no row in the table"); return RCN_ERR_NOT_FOUND; }
+        if (feat[e] < 0 || feat[e] >= it->second.second) { ctx->set_error(std::string(who) + ": feature " + std::to_string(feat[e]) + " of image " + std::to_string(img[e]) + " out of range"); return RCN_ERR_ARG; }
+        if (id[e] < -1) { ctx->set_error(std::string(who) + ": a landmark id is -1 (free) or >= 0"); return RCN_ERR_ARG; }
+        at[e] = it->second.first + feat[e];
+    }
+    RCN_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t b_at = al256(8 * (size_t)n);
+    RCN_HIP(ctx->lid_hws.reserve(b_at + al256(4 * (size_t)n)));
+    int64_t *d_at = ctx->lid_hws.as<int64_t>();
+    int32_t *d_id = reinterpret_cast<int32_t *>(ctx->lid_hws.as<char>() + b_at);
+    RCN_HIP(hipMemcpyAsync(d_at, at.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    RCN_HIP(hipMemcpyAsync(d_id, id, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    k_lid_scatter<<<(unsigned)((n + CB - 1) / CB), CB, 0, st>>>(d_at, d_id, n, ctx->lid.as<int32_t>());
+    RCN_HIP(hipGetLastError());
+    RCN_HIP(hipStreamSynchronize(st));                   // at is a local, id borrowed
+    return RCN_OK;
+}
+
+int rcn_landmark_ids_read(rcn_ctx *ctx, int32_t img, int32_t *out, int32_t K)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    const char *who = "rcn_landmark_ids_read";
+    if (K < 0 || (K > 0 && !out)) { ctx->set_error(std::string(who) + ": bad argument"); return RCN_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = lid_check(ctx, who);
+    if (rc) return rc;
+    auto it = ctx->lid_rows.find(img);
+    if (it == ctx->lid_rows.end()) { ctx->set_error(std::string(who) + ": image " + std::to_string(img) + " has no row in the table"); return RCN_ERR_NOT_FOUND; }
+    if (K != it->second.second) { ctx->set_error(std::string(who) + ": image " + std::to_string(img) + " has " + std::to_string(it->second.second) + " keypoints, not " + std::to_string(K)); return RCN_ERR_ARG; }
+    if (K == 0) return RCN_OK;
+    RCN_HIP(hipSetDevice(ctx->device));
+    RCN_HIP(hipMemcpyAsync(out, ctx->lid.as<int32_t>() + it->second.first, 4 * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
+    RCN_HIP(hipStreamSynchronize(ctx->stream));
+    return RCN_OK;
+}
+
+int rcn_new_view_tracks_device(rcn_ctx *ctx, int32_t v, int32_t n_reg, const int32_t *reg_img_host, int32_t cam_v,
+                               const int32_t *reg_cam_host, int32_t capacity, int32_t *n_tracks_dev, int32_t *trk_off_dev,
+                               int32_t *obs_cam_dev, int32_t *obs_xy_dev, int32_t *trk_src_dev)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    RCN_HIP(hipSetDevice(ctx->device));
+    return rcn_int_new_view_tracks(ctx, "rcn_new_view_tracks_device", v, n_reg, reg_img_host, cam_v, reg_cam_host, capacity, n_tracks_dev,
+                                   trk_off_dev, obs_cam_dev, obs_xy_dev, trk_src_dev);
+}
+
+int rcn_new_view_triangulate_device(rcn_ctx *ctx, int32_t v, int32_t n_reg, const int32_t *reg_img_host, int32_t cam_v,
+                                    const int32_t *reg_cam_host, int32_t n_cams, const double *poses34_dev, const double *intrinsics_dev,
+                                    double max_projection_error, double min_triangulation_angle, int32_t first_landmark, int32_t capacity,
+                                    int32_t *n_tracks_dev, int32_t *trk_off_dev, int32_t *obs_cam_dev, int32_t *obs_xy_dev,
+                                    int32_t *trk_src_dev, double *out_xyz_dev, uint8_t *out_status_dev, double *out_compact_dev,
+                                    int32_t compact_first, int32_t *out_n_accepted_dev)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    const char *who = "rcn_new_view_triangulate_device";
+    if (n_cams < 1 || !poses34_dev || !intrinsics_dev || first_landmark < 0 || compact_first < 0 || !out_n_accepted_dev ||
+        (capacity > 0 && (!out_xyz_dev || !out_status_dev)) || cam_v < 0 || cam_v >= n_cams) {
+        ctx->set_error(std::string(who) + ": bad argument");
+        return RCN_ERR_ARG;
+    }
+    for (int32_t k = 0; k < n_reg && reg_cam_host; ++k)
+        if (reg_cam_host[k] < 0 || reg_cam_host[k] >= n_cams) { ctx->set_error(std::string(who) + ": camera row out of range"); return RCN_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    RCN_HIP(hipSetDevice(ctx->device));
+    int rc = rcn_int_new_view_tracks(ctx, who, v, n_reg, reg_img_host, cam_v, reg_cam_host, capacity, n_tracks_dev, trk_off_dev, obs_cam_dev,
+                                     obs_xy_dev, trk_src_dev);
+    if (rc) return rc;
+    RCN_HIP(ctx->tri_dws.reserve(rcn_int_triangulate_ws_bytes(n_cams, capacity)));
+    rcn_triangulation_problem dp{n_cams, capacity, 2 * capacity, 0, poses34_dev, intrinsics_dev, trk_off_dev, obs_cam_dev, obs_xy_dev};
+    rc = rcn_int_triangulate_launch(ctx, &dp, max_projection_error, min_triangulation_angle, ctx->tri_dws.p, out_xyz_dev, out_status_dev,
+                                    out_compact_dev, compact_first, out_n_accepted_dev);
+    if (rc) return rc;
+    return rcn_int_new_view_commit(ctx, v, capacity, n_tracks_dev, trk_src_dev, out_status_dev, first_landmark);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int rcn_corr_set_workspace_bytes(rcn_ctx *ctx, int64_t bytes)
@@ -490,6 +806,7 @@ int rcn_match_lists_clear(rcn_ctx *ctx)
     RCN_HIP(hipSetDevice(ctx->device));
     RCN_HIP(hipStreamSynchronize(ctx->stream));
     ctx->corr.release();
+    ++ctx->lists_gen;
     return RCN_OK;
 }
 
@@ -553,6 +870,7 @@ int rcn_match_lists_upload(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, 
     RCN_HIP(hipStreamSynchronize(st));
     CorrLists &L = ctx->corr;
     L.release();
+    ++ctx->lists_gen;
     RCN_HIP(L.ent.reserve(8 * (size_t)std::max<int64_t>(n_ent, 1)));
     RCN_HIP(L.list_off.reserve(8 * (size_t)(n_pairs + 1)));
     RCN_HIP(L.dir.reserve(4 * dir.size()));

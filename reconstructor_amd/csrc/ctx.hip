@@ -105,6 +105,8 @@ void rcn_destroy(rcn_ctx *ctx)
     ctx->corr.release();
     ctx->corr_ws.release(); ctx->corr_hws.release(); ctx->corr_slots.release(); ctx->att_ws.release();
     if (ctx->corr_ev) (void)hipEventDestroy(ctx->corr_ev);
+    ctx->lid.release(); ctx->lid_slot_off.release(); ctx->lid_hws.release(); ctx->nvt_ws.release();
+    if (ctx->nvt_ev) (void)hipEventDestroy(ctx->nvt_ev);
     ctx->pnp_hws.release(); ctx->pnp_slots.release();
     ctx->tv_hws.release(); ctx->tv_dws.release(); ctx->tv_fws.release();
     if (ctx->tv_ev) (void)hipEventDestroy(ctx->tv_ev);

@@ -752,6 +752,7 @@ extern "C" int rcn_coords_upload(rcn_ctx *ctx, int32_t img_id, const int32_t *xy
     if (K < 0 || (K > 0 && !xy_host)) { ctx->set_error("rcn_coords_upload: bad argument"); return RCN_ERR_ARG; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     RCN_HIP(hipSetDevice(ctx->device));
+    ++ctx->coords_gen;
     auto &e = ctx->coords[img_id];
     RCN_HIP(e.first.reserve(std::max<size_t>(8 * (size_t)K, 8)));
     if (K > 0) {
@@ -771,6 +772,7 @@ extern "C" int rcn_coords_upload_batch(rcn_ctx *ctx, int32_t first_img_id, int32
         if (K[i] < 0 || (K[i] > 0 && !xy_host[i])) { ctx->set_error("rcn_coords_upload_batch: bad row count or NULL coordinates"); return RCN_ERR_ARG; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     RCN_HIP(hipSetDevice(ctx->device));
+    ++ctx->coords_gen;
     for (int i = 0; i < n_images; ++i) {
         auto &e = ctx->coords[first_img_id + i];
         RCN_HIP(e.first.reserve(std::max<size_t>(8 * (size_t)K[i], 8)));
@@ -789,6 +791,7 @@ extern "C" int rcn_coords_clear(rcn_ctx *ctx)
     RCN_HIP(hipStreamSynchronize(ctx->stream));
     for (auto &kv : ctx->coords) kv.second.first.release();
     ctx->coords.clear();
+    ++ctx->coords_gen;
     return RCN_OK;
 }
 

@@ -245,6 +245,16 @@ struct rcn_ctx {
     hipEvent_t tv_ev = nullptr;
     bool tv_stage_pending = false;
     int64_t corr_budget = 1ll << 30;    // bytes of hit rows per batch (rcn_corr_set_workspace_bytes)
+    // landmark-id table (corr2d3d.hip, rcn_landmark_ids_*): one int32 per keypoint of every image with resident coordinates
+    DevBuf lid, lid_slot_off, lid_hws;  // the table, first entry of every list slot's row (int64), staging of rcn_landmark_ids_set
+    std::map<int32_t, std::pair<int64_t, int32_t>> lid_rows;   // image id -> (first entry, K) at the last reset
+    bool lid_live = false;
+    uint64_t coords_gen = 0, lists_gen = 0;         // bumped by every change of the resident coordinates / match lists
+    uint64_t lid_coords_gen = 0, lid_lists_gen = 0; // ... as they stood at the last reset: the table is valid while both are unchanged
+    DevBuf nvt_ws;                      // new-view candidates (corr2d3d.hip): registered-image table, best (position, partner) per feature
+    std::vector<char> nvt_stage_host;   // staging of the registered-image table (uploaded asynchronously; nvt_ev marks the copy)
+    hipEvent_t nvt_ev = nullptr;
+    bool nvt_stage_pending = false;
     std::vector<int> ba_graph_cam, ba_graph_pt;     // observation graph of the last plain rcn_ba_solve (host copy): an identical graph reuses the pair lists
     int ba_graph_nc = 0, ba_graph_np = 0;
     uint64_t ba_graph_serial = 0;
@@ -308,6 +318,15 @@ size_t rcn_int_attach_ws_bytes(int32_t n_feat);
 int rcn_int_attach_launch(rcn_ctx *ctx, const double *P, const double *K, const double *pts, int32_t n_points, int32_t n,
                           const int32_t *lm, const int32_t *feat, const int32_t *xy, int32_t n_feat, double max_err,
                           uint8_t *status, void *ws);
+// corr2d3d.hip, with ctx->mu held: step 3 of triangulateMatchedLandmarks on the resident lists and the landmark-id table
+// (rcn_new_view_tracks_device's body: checks, one staged copy, launches), the commit of the accepted tracks' landmark indices into
+// the table, and the rows an image has in the resident coordinates (-1: none)
+int rcn_int_new_view_tracks(rcn_ctx *ctx, const char *who, int32_t v, int32_t n_reg, const int32_t *reg_img, int32_t cam_v,
+                            const int32_t *reg_cam, int32_t capacity, int32_t *n_tracks_dev, int32_t *trk_off_dev,
+                            int32_t *obs_cam_dev, int32_t *obs_xy_dev, int32_t *trk_src_dev);
+int rcn_int_new_view_commit(rcn_ctx *ctx, int32_t v, int32_t capacity, const int32_t *n_tracks_dev, const int32_t *trk_src_dev,
+                            const uint8_t *status_dev, int32_t first_landmark);
+int32_t rcn_int_coords_rows(rcn_ctx *ctx, int32_t img);
 // store.hip: rcn_match_compact_begin / _wait with ctx->mu already held
 int rcn_int_compact_begin(rcn_ctx *ctx, const int32_t *table_dev, int64_t stride, const int32_t *counts_dev,
                           int32_t n_pairs, int64_t *offsets_host, int32_t *qt_host, int64_t capacity, int64_t *total_out);
