@@ -896,22 +896,27 @@ __device__ __forceinline__ int key_idx(const ScaleDev &S, unsigned k, uint32_t m
 // maxima rho >= |rt|, tau >= |tq| over every converted row
 //     |acc - (s^2 |t|^2 / 2 - s^2 q.t + BIAS)| <= |qq| rho + |rq| tau + |rq| rho + 0.5      (0.5: the rounding of the integer half-norm)
 // -- nothing else: the integer accumulation is exact.  (1e-3 on top: the fp64 evaluation of half_s2 * |t|^2 before its rounding, and of this sum.)
+__device__ __forceinline__ double coarse_eps_i8n(const ScaleDev &S, float2 n, double nq2)      // n: the row's ImgDev::i8n entry (int8 path; not read otherwise)
+{
+    if (!S.coarse_i8) return coarse_eps(S, nq2);
+    return ((double)n.x * S.rho + (double)n.y * (S.tau + S.rho)) * (1.0 + 1e-9) + 0.5 + 1.0e-3;
+}
 __device__ __forceinline__ double coarse_eps_row(const ScaleDev &S, const ImgDev &qi, int q, double nq2)
 {
     if (!S.coarse_i8) return coarse_eps(S, nq2);
-    const float2 n = qi.i8n[q];
-    return ((double)n.x * S.rho + (double)n.y * (S.tau + S.rho)) * (1.0 + 1e-9) + 0.5 + 1.0e-3;
+    return coarse_eps_i8n(S, qi.i8n[q], nq2);
 }
 
 // lower bound on the exact squared distance from a query of squared norm nq2 to ANY BIG row of an image: (|t| - |q|)^2 with
 // |t| >= the image's smallest BIG norm, evaluated with a relative slack; +infinity when the image has no BIG row
-__device__ __forceinline__ double big_lower_bound(const unsigned long long *bigmin, double nq2)
+__device__ __forceinline__ double big_lower_bound_bits(unsigned long long bigmin_bits, double nq2)
 {
-    const double b2 = __longlong_as_double((long long)*bigmin);
+    const double b2 = __longlong_as_double((long long)bigmin_bits);
     if (!(b2 <= 1.7976931348623157e308)) return b2;                 // +infinity
     const double d = sqrt(b2) * (1.0 - 1e-12) - sqrt(nq2) * (1.0 + 1e-12);
     return d > 0.0 ? d * d * (1.0 - 1e-9) : 0.0;
 }
+__device__ __forceinline__ double big_lower_bound(const unsigned long long *bigmin, double nq2) { return big_lower_bound_bits(*bigmin, nq2); }
 
 // Integer threshold of the middle tier (k_mid_eval_i8, mid_i8.h) for a row that leaves the re-rank (0: none, the row keeps the fp32 sweep).
 // eb = the larger of the two candidates' exact distances: an upper bound of the exact SECOND-nearest distance.  With
@@ -919,13 +924,19 @@ __device__ __forceinline__ double big_lower_bound(const unsigned long long *bigm
 // a row t with exact d2(q, t) <= eb has real-valued accumulator A*(t) <= accof(eb) and |acc(t) - A*(t)| <= E(q) (coarse_eps_row), so
 // acc(t) <= accof(eb) + E(q), and acc(t) being an integer, acc(t) <= floor(accof(eb) + E(q)).  One more for the fp64 evaluation of
 // the bound (the slack widens eb the way lbnc's narrows its bound).
-__device__ __forceinline__ unsigned mid_thr_acc(const ScaleDev &S, const ImgDev &qi, int q, double nq2, double eb, unsigned key2, uint32_t mask)
+// (eps: coarse_eps_row of the query row, for a caller that has it already)
+__device__ __forceinline__ unsigned mid_thr_acc_eps(const ScaleDev &S, double eps, double nq2, double eb, unsigned key2, uint32_t mask)
 {
     if (!S.coarse_i8 || key_is_pad(S, key2, mask) || !(fabs(eb) <= 1.7976931348623157e308)) return 0u;
     const double d2 = eb * (1.0 + S.rel_slack) + S.rel_slack * (nq2 + S.n_max * S.n_max);
-    const double v = floor(S.bias + S.hs2 * (d2 - nq2) + coarse_eps_row(S, qi, q, nq2)) + 1.0;
+    const double v = floor(S.bias + S.hs2 * (d2 - nq2) + eps) + 1.0;
     if (!(v >= 1.0) || v >= (double)RCN_I8_PAD_ACC) return 0u;
     return (unsigned)v;
+}
+__device__ __forceinline__ unsigned mid_thr_acc(const ScaleDev &S, const ImgDev &qi, int q, double nq2, double eb, unsigned key2, uint32_t mask)
+{
+    if (!S.coarse_i8) return 0u;      // (no int8 rows: never a threshold, and qi.i8n is not there to read)
+    return mid_thr_acc_eps(S, coarse_eps_row(S, qi, q, nq2), nq2, eb, key2, mask);
 }
 
 __device__ __forceinline__ void list_append(unsigned long long *list, unsigned *count, bool want,
@@ -1048,93 +1059,102 @@ __global__ __launch_bounds__(RCN_FT) void k_filter(RerankArgs a)
     }
 }
 
-// K2: exact fp64 re-rank of the survivors.  Only the BEST coarse candidate is re-computed:
-// every other row -- the second candidate included -- has accumulator >= trunc(second), hence
-// exact distance >= lbnc, so  ea < lbnc  proves the candidate is the nearest neighbour and
-// ratio_pass(ea, lbnc) proves the ratio test for whatever the true second distance is.  Rows
-// that this does not certify (a few hundred in ten million) go to the exact kernel.
-// One wave = 64 survivors.  Rows are staged through LDS in 32-float chunks so that global reads
-// are whole 128-B segments (8 lanes per row) instead of 64 lanes striding 1-KiB rows; each
-// lane then walks its (query, candidate) chain in ascending k out of LDS.
-// (round 4, second session) BOTH coarse candidates go through the chain: with the second exact distance in hand `certify` can also
-// say "no match" -- every row but the two candidates is at least lbnc away, so the exact second neighbour lies in [min(eb, lbnc), eb],
-// and a ratio test that fails against eb fails for whatever it is -- where round 3 sent every row it could not PASS to the next tier.
-#define RR_ROWS 192
-#define RR_LD 36  // floats per LDS row: 32 + 4 pad (conflict-free ds_read_b128 by row)
+// K2: exact fp64 re-rank of the survivors.  BOTH coarse candidates go through the canonical chain: every other row has accumulator
+// >= trunc(second), hence exact distance >= lbnc, so with the two exact distances in hand `certify` can say "this candidate, and the
+// ratio test passes whatever the true second distance is" or "no match" -- every row but the two candidates is at least lbnc away, so
+// the exact second neighbour lies in [min(eb, lbnc), eb], and a ratio test that fails against eb fails for whatever it is.  Rows that
+// this does not certify go to the next tier.
+// The int8 coarse pass sends 24.8 M rows per cfg-3 step here, three random 1-KiB rows each: the kernel is a gather, and it is built as
+// exact_gather.h says.  A workgroup is ONE wave with a tile of its own: RR_B survivors = 3 RR_B whole rows (query, first and second
+// candidate), lanes 0 .. 2 RR_B - 1 own one chain each.  The next tile's rows are requested before the chains of the present one run,
+// and the row addresses of the tile after that are looked up (survivor -> pair -> images -> candidates: dependent loads) behind the
+// chains, while those requests are still in flight.  25 KiB of LDS: six workgroups per CU, 144 KiB of rows in flight per CU.
+#include "exact_gather.h"
+#define RR_B (XG_ROWS / 3)
+struct RrRows {                 // lane l: survivor l % RR_B of the tile, role l / RR_B (0 query row, 1 first, 2 second candidate)
+    unsigned long long e;
+    uint2 c;
+    const float *ptr;           // this lane's row; nullptr: none
+    double nq2;                 // what `certify` needs besides the chains, fetched a tile ahead like the rows (lanes < RR_B of a live survivor
+    float2 i8n;                 // that can be certified): the query row's squared norm and int8 norms, the train image's smallest BIG norm
+    unsigned long long bigmin;
+    int32_t ia, ib, tK;
+};
+__device__ __forceinline__ RrRows rr_rows(const RerankArgs &a, const ScaleDev &S, unsigned g, unsigned n)
+{
+    RrRows m;
+    const int lane = threadIdx.x & 63;
+    const unsigned sidx = g * RR_B + (lane % RR_B);
+    const bool live = sidx < n && lane < XG_ROWS;
+    m.e = a.sv_list[live ? sidx : g * RR_B];
+    const int pair = (int)(m.e >> 32), q = (int)(m.e & 0xFFFFFFFFu);
+    const ImgDev &qi = a.imgs[a.pairs[2 * pair]], &ti = a.imgs[a.pairs[2 * pair + 1]];
+    m.c = a.cand[(size_t)pair * a.kq_stride + q];
+    const float *qf = qi.f32, *tf = ti.f32;
+    m.tK = ti.K;
+    m.ia = key_idx(S, m.c.x, a.idx_mask); m.ib = key_idx(S, m.c.y, a.idx_mask);
+    if (m.ib >= m.tK) m.ib = m.ia;      // (a padding row as second candidate: k_filter keeps such rows off this list; never an address)
+    const int role = lane / RR_B;
+    m.ptr = !live ? nullptr : role == 0 ? qf + (size_t)q * a.D : tf + (size_t)(role == 1 ? m.ia : m.ib) * a.D;
+    m.nq2 = 0.0; m.i8n = make_float2(0.f, 0.f); m.bigmin = 0ull;
+    if (live && role == 0 && m.tK > 2 && m.ib != m.ia) {
+        m.nq2 = qi.nrm2[q];
+        if (S.coarse_i8) m.i8n = qi.i8n[q];
+        m.bigmin = *ti.bigmin;
+    }
+    return m;
+}
 __global__ __launch_bounds__(64) void k_rerank_lds(RerankArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float tile[RR_ROWS * RR_LD];
-    __shared__ const float *rowptr[RR_ROWS];
+    __shared__ __attribute__((aligned(16))) float tile[XG_TILEF];
+    __shared__ XgPend pend;
     const int lane = threadIdx.x;
     const unsigned n = *a.sv_count;
+    const unsigned ntile = (n + RR_B - 1) / RR_B;
     const int D = a.D;
-    const int nchunk = (D + 31) / 32;
     const ScaleDev S = *a.sc;
-    for (unsigned g = blockIdx.x; g * 64u < n; g += gridDim.x) {
-        const unsigned sidx = g * 64u + lane;
-        const bool live = sidx < n;
-        const unsigned long long e = a.sv_list[live ? sidx : g * 64u];
-        const int pair = (int)(e >> 32), q = (int)(e & 0xFFFFFFFFu);
-        const ImgDev qi = a.imgs[a.pairs[2 * pair]];
-        const ImgDev ti = a.imgs[a.pairs[2 * pair + 1]];
-        const uint2 c = a.cand[(size_t)pair * a.kq_stride + q];
-        int ia = key_idx(S, c.x, a.idx_mask), ib = key_idx(S, c.y, a.idx_mask);
-        if (ib >= ti.K) ib = ia;      // (a padding row as second candidate: k_filter keeps such rows off this list; never an address)
-        __syncthreads();  // previous group's reads of rowptr/tile are done
-        rowptr[lane] = qi.f32 + (size_t)q * D;
-        rowptr[64 + lane] = ti.f32 + (size_t)ia * D;
-        rowptr[128 + lane] = ti.f32 + (size_t)ib * D;
-        __syncthreads();
-        double acc = 0.0, acc2 = 0.0;
-        const float *qrow = tile + lane * RR_LD;
-        const float *trow = tile + (64 + lane) * RR_LD;
-        const float *trow2 = tile + (128 + lane) * RR_LD;
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int col = ch * 32 + (lane & 7) * 4;
-#pragma unroll
-            for (int i = 0; i < RR_ROWS / 8; ++i) {
-                const int r = i * 8 + (lane >> 3);
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (col < D) v = *reinterpret_cast<const float4 *>(rowptr[r] + col);
-                *reinterpret_cast<float4 *>(tile + r * RR_LD + (lane & 7) * 4) = v;
-            }
-            __syncthreads();
-            const int kmax = min(32, D - ch * 32);
-            for (int k4 = 0; k4 < kmax; k4 += 4) {
-                const float4 x = *reinterpret_cast<const float4 *>(qrow + k4);
-                const float4 y = *reinterpret_cast<const float4 *>(trow + k4);
-                const float4 z = *reinterpret_cast<const float4 *>(trow2 + k4);
-                double d;
-                d = (double)x.x - (double)y.x; acc = fma(d, d, acc);
-                d = (double)x.y - (double)y.y; acc = fma(d, d, acc);
-                d = (double)x.z - (double)y.z; acc = fma(d, d, acc);
-                d = (double)x.w - (double)y.w; acc = fma(d, d, acc);
-                d = (double)x.x - (double)z.x; acc2 = fma(d, d, acc2);
-                d = (double)x.y - (double)z.y; acc2 = fma(d, d, acc2);
-                d = (double)x.z - (double)z.z; acc2 = fma(d, d, acc2);
-                d = (double)x.w - (double)z.w; acc2 = fma(d, d, acc2);
-            }
-            __syncthreads();
-        }
+    unsigned g = blockIdx.x, np = 0;
+    if (g >= ntile) return;
+    float4 v[XG_ROWS];
+    RrRows m0 = rr_rows(a, S, g, n), m1 = m0;
+    unsigned rows = xg_issue(v, m0.ptr, D);
+    if (g + gridDim.x < ntile) m1 = rr_rows(a, S, g + gridDim.x, n);
+    xg_store(tile, v, rows);
+    for (; g < ntile; g += gridDim.x) {
+        const bool more = g + gridDim.x < ntile;
+        if (more) rows = xg_issue(v, m1.ptr, D);
+        __builtin_amdgcn_wave_barrier();
+        // lanes 0 .. RR_B - 1: query x first candidate, lanes RR_B .. 2 RR_B - 1: query x second candidate
+        double acc = 0.0;
+        if (lane < 2 * RR_B) acc = xg_chain(tile, lane % RR_B, RR_B + lane, D);
+        const double acc2 = __shfl(acc, lane + RR_B);
         bool fb = false;
         unsigned tacc = 0u;
-        if (live) {
+        if (lane < RR_B && g * RR_B + lane < n) {
+            const int pair = (int)(m0.e >> 32), q = (int)(m0.e & 0xFFFFFFFFu);
+            const uint2 c = m0.c;
+            int ia = m0.ia, ib = m0.ib;
             // the two candidates ordered by (exact value, index), as the oracle's scan would meet them
             double ea = acc, eb = acc2;
             if (ib != ia && (eb < ea || (eb == ea && ib < ia))) { ea = acc2; eb = acc; const int t = ia; ia = ib; ib = t; }
             int res = -2;
-            if (ti.K > 2 && ib != ia) {
-                const double nq2 = qi.nrm2[q];
+            if (m0.tK > 2 && ib != ia) {
+                const double nq2 = m0.nq2, eps = coarse_eps_i8n(S, m0.i8n, nq2);
                 const double lbacc = key_lo(S, c.y, a.idx_mask);
-                const double lbnc = fmin(acc_to_d2(S, nq2, lbacc - coarse_eps_row(S, qi, q, nq2)) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound(ti.bigmin, nq2));
+                const double lbnc = fmin(acc_to_d2(S, nq2, lbacc - eps) - S.rel_slack * (nq2 + S.n_max * S.n_max), big_lower_bound_bits(m0.bigmin, nq2));
                 res = RCN_RERANK_PASS(a) ? -2 : certify(ea, ia, eb, lbnc, a.ratio);
-                if (res == -2 && a.fb_tacc) tacc = mid_thr_acc(S, qi, q, nq2, eb, c.y, a.idx_mask);
+                if (res == -2 && a.fb_tacc) tacc = mid_thr_acc_eps(S, eps, nq2, eb, c.y, a.idx_mask);
             }
             if (res >= 0) a.out[(size_t)pair * a.out_stride + q] = res;
             else if (res == -2) fb = true;   // out stays -1 (which is also the certified "no match") until the next tier decides
         }
-        list_append(a.fb_list, a.fb_count, fb, e, a.fb_tacc, tacc);
+        xg_pend_add(pend, np, fb, m0.e, tacc, a.fb_list, a.fb_count, a.fb_tacc);
+        m0 = m1;
+        if (g + 2 * gridDim.x < ntile) m1 = rr_rows(a, S, g + 2 * gridDim.x, n);
+        __builtin_amdgcn_wave_barrier();
+        if (more) xg_store(tile, v, rows);
     }
+    xg_pend_flush(pend, np, a.fb_list, a.fb_count, a.fb_tacc);
 }
 
 // generic survivor re-rank (D not a multiple of 4): one thread per survivor
@@ -1687,8 +1707,97 @@ __global__ __launch_bounds__(256, 4) void k_mid_eval(MidArgs a)
     }
 }
 #include "mid_i8.h"
-// one wave per row of the tier: the canonical fp64 chain of its candidates, (value, index)-ordered top-2, ratio test
-__global__ __launch_bounds__(256) void k_mid_exact(MidArgs a)
+// The rows of the tier: the canonical fp64 chain of each row's candidates, (value, index)-ordered top-2, ratio test.
+// On the gather of exact_gather.h (D <= XG_ROWF): a wave takes MX_Q rows of the tier at a time; tile rows 0 .. MX_Q - 1 are their query
+// rows and the other MX_C tile rows take the candidates of all of them, in the order of the rows, MX_C per pass (a row has two to
+// RCN_MIDCAP candidates, a handful as a rule: one pass).  Lane c owns the chain of candidate row c of the pass; the owners of the tier
+// rows (lanes < MX_Q) then merge their own candidates' (value, index) from LDS.  No double buffer here: six independent one-wave
+// workgroups per CU overlap their requests, 4 + 12 KiB a wave for rows of three candidates.
+#define MX_Q 4
+#define MX_C (XG_ROWS - MX_Q)
+__global__ __launch_bounds__(64) void k_mid_exact(MidArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float tile[XG_TILEF];
+    __shared__ double sd[MX_C];
+    __shared__ int sj[MX_C];
+    const int lane = threadIdx.x;
+    const unsigned n = mid_rows(a);
+    const unsigned ngroup = (n + MX_Q - 1) / MX_Q;
+    const int D = a.D;
+    float4 v[XG_ROWS];
+    for (unsigned g = blockIdx.x; g < ngroup; g += gridDim.x) {
+        const unsigned r = g * MX_Q + lane;
+        const bool own = lane < MX_Q && r < n;
+        unsigned long long e = 0ull;
+        unsigned cnt = 0u;
+        unsigned long long qp = 0ull, tf = 0ull;      // the query row, the train image's rows (addresses)
+        bool decide = false;
+        if (own) {
+            e = a.sorted[r];
+            cnt = a.ccount[r];
+            if (cnt > (unsigned)RCN_MIDCAP) {                   // more rows under the threshold than the list holds: every train row, K2b
+                a.fb2_list[atomicAdd(a.fb2_count, 1u)] = e;
+                cnt = 0u;
+            } else {
+                const int pair = (int)(e >> 32), q = (int)(e & 0xFFFFFFFFu);
+                qp = reinterpret_cast<unsigned long long>(a.imgs[a.pairs[2 * pair]].f32 + (size_t)q * D);
+                tf = reinterpret_cast<unsigned long long>(a.imgs[a.pairs[2 * pair + 1]].f32);
+                decide = true;
+            }
+        }
+        unsigned pre[MX_Q + 1], mine = 0u;        // candidates in front of tier row t of the group (uniform); of this lane's own row
+        pre[0] = 0u;
+#pragma unroll
+        for (int t = 0; t < MX_Q; ++t) {
+            pre[t + 1] = pre[t] + (unsigned)__shfl((int)cnt, t);
+            if (lane > t) mine = pre[t + 1];
+        }
+        const unsigned total = pre[MX_Q];
+        double b0 = INFINITY, b1 = INFINITY;
+        int i0 = 0x7FFFFFFF, i1 = 0x7FFFFFFF;
+        for (unsigned base = 0; base < total; base += MX_C) {
+            const unsigned j = base + lane;                   // lane c < MX_C: candidate j of the group
+            const bool cl = lane < MX_C && j < total;
+            int t = 0;
+            unsigned pt = 0u;
+#pragma unroll
+            for (int tt = 1; tt < MX_Q; ++tt)
+                if (j >= pre[tt]) { t = tt; pt = pre[tt]; }
+            const unsigned long long tft = __shfl(tf, t);
+            int idx = 0x7FFFFFFF;
+            unsigned long long cp = 0ull;
+            if (cl) {
+                idx = a.clist[(size_t)(g * MX_Q + t) * RCN_MIDCAP + (j - pt)];
+                cp = reinterpret_cast<unsigned long long>(reinterpret_cast<const float *>(tft) + (size_t)idx * D);
+            }
+            const unsigned long long cps = __shfl(cp, lane - MX_Q);
+            const unsigned long long ptr = lane < MX_Q ? (base == 0 ? qp : 0ull) : lane < XG_ROWS ? cps : 0ull;
+            const unsigned rows = xg_issue(v, reinterpret_cast<const float *>(ptr), D);
+            xg_store(tile, v, rows);
+            __builtin_amdgcn_wave_barrier();
+            double d = INFINITY;
+            if (cl) d = xg_chain(tile, t, MX_Q + lane, D);
+            if (lane < MX_C) { sd[lane] = d; sj[lane] = idx; }
+            __builtin_amdgcn_wave_barrier();
+            if (decide) {
+                const unsigned lo = max(mine, base), hi = min(mine + cnt, base + MX_C);
+                for (unsigned jj = lo; jj < hi; ++jj) {
+                    const double c0 = sd[jj - base];
+                    if (c0 < INFINITY)                      // K2b never selects a row whose distance is not below +infinity
+                        merge_top2(b0, i0, b1, i1, c0, sj[jj - base], INFINITY, 0x7FFFFFFF);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (decide) {
+            const int pair = (int)(e >> 32), q = (int)(e & 0xFFFFFFFFu);
+            a.out[(size_t)pair * a.out_stride + q] = ratio_pass(b0, b1, a.ratio) ? i0 : -1;
+        }
+    }
+}
+
+// the same for rows longer than a tile row: one wave per row of the tier, one lane per candidate straight from global memory
+__global__ __launch_bounds__(256) void k_mid_exact_wide(MidArgs a)
 {
     const unsigned n = mid_rows(a);
     const int lane = threadIdx.x & 63;
@@ -1806,6 +1915,25 @@ static int pad_dim(int D)
     if (D <= 128) return 128;
     if (D <= 256) return 256;
     return 0;  // no MFMA path
+}
+
+// The gather kernels are persistent (a wave walks its tiles): as many one-wave workgroups as are resident at once.
+template <typename Kernel>
+static int resident_grid(rcn_ctx *ctx, Kernel kernel, int &per_cu)
+{
+    if (per_cu <= 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64, 0) != hipSuccess || nb < 1) nb = 4;
+        per_cu = nb;
+    }
+    return ctx->prop.multiProcessorCount * per_cu;
+}
+static int rerank_grid(rcn_ctx *ctx) { static int per_cu = 0; return resident_grid(ctx, k_rerank_lds, per_cu); }
+static void launch_mid_exact(rcn_ctx *ctx, const MidArgs &ma, hipStream_t st)
+{
+    static int per_cu = 0;
+    if (ma.D <= XG_ROWF) k_mid_exact<<<resident_grid(ctx, k_mid_exact, per_cu), 64, 0, st>>>(ma);
+    else k_mid_exact_wide<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
 }
 
 static hipError_t launch_rowstats(rcn_ctx *ctx, const float *x, int rows, int D, double *nrm2, unsigned *cnt)
@@ -2635,7 +2763,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
             // coarse pass runs on the fp16 payload; the exact stages are the first to read them
             if (ctx->f32_ready) RCN_HIP(hipStreamWaitEvent(st, ctx->f32_ready, 0));
             if (mfma) {
-                if (vec4) k_rerank_lds<<<ctx->prop.multiProcessorCount * 16, 64, 0, st>>>(ra);
+                if (vec4) k_rerank_lds<<<rerank_grid(ctx), 64, 0, st>>>(ra);
                 else k_rerank_generic<<<ctx->prop.multiProcessorCount * 8, 256, 0, st>>>(ra);
                 RCN_HIP(hipGetLastError());
             }
@@ -2667,7 +2795,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
                 k_mid_scatter<<<mb, 256, 0, st>>>(ma);
                 k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
                 if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
-                k_mid_exact<<<mb, 256, 0, st>>>(ma);
+                launch_mid_exact(ctx, ma, st);
                 RCN_HIP(hipGetLastError());
                 // K2b: the overflow list, then the rows beyond the tier's budget (none unless a chunk leaves more than RCN_MIDROWS rows)
                 if (vec4) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ma.fb2_list, ma.fb2_count, ctx->D, ratio, out_dev, out_stride);
@@ -2716,7 +2844,7 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
         k_mid_scatter<<<mb, 256, 0, st>>>(ma);
         k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
         if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
-        k_mid_exact<<<mb, 256, 0, st>>>(ma);
+        launch_mid_exact(ctx, ma, st);
         k_exact_rows_lds<<<ctx->prop.multiProcessorCount * 8, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ma.fb2_list, ma.fb2_count, ctx->D, ratio, out_dev, out_stride);
         k_stats_acc_deferred<<<1, 64, 0, st>>>(ccnt);
         RCN_HIP(hipGetLastError());
