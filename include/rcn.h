@@ -1104,6 +1104,60 @@ int  rcn_retr_pairs_device(rcn_ctx *ctx, const int32_t *nbr_dev, int32_t n, int3
 int  rcn_retr_image_pairs(rcn_ctx *ctx, const rcn_retr_codebook *cb, const float *desc_dev, const int32_t *counts_dev, int32_t n, int32_t K,
                           int32_t D, int32_t first_img_id, int32_t top_k, int32_t *pairs_host, int64_t capacity, int32_t *n_pairs_out);
 
+/* ---- image preparation: what detectFeatures does to a photograph before the detector sees it -------------------------
+ * Utils::readImg (BGR -> RGB, reshapeImg = cv::resize to at most imgMaxSize on the longer side, the other side cut down to
+ * a multiple of 8), cv::cvtColor(RGB2GRAY), the colour under every feature (SequentialReconstructor.cpp:55-110), a
+ * landmark's colour (:429-433) and Utils::saveCloud (utils.cpp:205-275, :345-368).  Defined by tests/img_ref.py (DESIGN
+ * section 26): cv::resize's default INTER_LINEAR for 8-bit data in its 11-bit fixed point, its 2 x 2 area branch when both
+ * axes halve, a copy at equal sizes; every output byte equals the restatement.  JPEG decoding stays with the caller.
+ *
+ * rcn_img_reshape_size and rcn_img_resize_tables are pure host code (no device needed).  The tables of one axis: for output
+ * position d, index_out[d] is the left / upper source pixel -- clamped to 0 .. src - 1 on the horizontal axis, floor(f)
+ * itself (-1 .. src - 1) on the vertical one, where it is clipped together with its successor -- and weights_out[d] the two
+ * 11-bit weights, which sum to 2048.  *xmax_out (may be NULL): the first d that reads a single pixel at the right border
+ * (dst: none, and always on the vertical axis).  They are built in the float / double operations of resize.cpp, in a
+ * translation unit compiled without contraction, and uploaded per call; the kernels do integer arithmetic only. */
+#define RCN_IMG_RGB 0
+#define RCN_IMG_BGR 1
+int  rcn_img_reshape_size(int32_t rows, int32_t cols, int32_t max_size, int32_t *rows_out, int32_t *cols_out, double *factor_out);
+int  rcn_img_resize_tables(int32_t src, int32_t dst, int32_t horizontal, int32_t *index_out /*[dst]*/, int16_t *weights_out /*[dst][2]*/,
+                           int32_t *xmax_out);
+typedef struct { int32_t order /*RCN_IMG_RGB | RCN_IMG_BGR*/, gray_bits /*14 | 15*/; } rcn_img_options;
+void rcn_img_default_options(rcn_img_options *opt);      /* BGR (what imread delivers), 14 (OpenCV 4.2's table; 15: later releases) */
+/* The tile rcn_img_prepare_device works in for this horizontal resize: tile_cols x tile_rows output pixels per workgroup, their
+ * source spans staged in lds_bytes of LDS.  tile_rows shrinks as the horizontal scale grows (8, 4, 2, 1); 0: the spans of even
+ * one row do not fit, and the one-row tile reads its source pixels from memory directly.  Pure host code. */
+int  rcn_img_prepare_plan(int32_t src_cols, int32_t cols, int32_t channels, int32_t *tile_cols, int32_t *tile_rows, int32_t *lds_bytes);
+/* n images of one source size, interleaved pixels, rows stride_row_bytes apart (padding allowed, as cv::Mat::step), images
+ * stride_img_bytes apart -> rgb_out [n][rows][cols][3] in the order red, green, blue and gray_out [n][rows][cols], either of
+ * which may be NULL.  channels == 1: gray_out is the resized plane (readGrayImg + reshapeImg) and rgb_out must be NULL.  One
+ * kernel: swap, both resize passes and the grey conversion of the RESIZED colours.  An image's bytes do not depend on n, on
+ * the strides, on its position in the batch or on the tile.  opt == NULL: the defaults.
+ * RCN_ERR_ARG: a null required pointer, both outputs NULL, channels not 1 or 3, a non-positive size, n < 0, a row stride below
+ * src_cols * channels, rows * cols * 3 > 2^31 - 1, an unknown option value, a destination of more than 2^24 - 1 tiles (a launch
+ * holds fewer than 2^32 work-items: only a destination a few pixels wide and tens of millions of rows high reaches that; the
+ * gathers below refuse n * K, and 2 L + C, beyond 2^32 - 256 for the same reason).  n == 0 launches nothing. */
+int  rcn_img_prepare_device(rcn_ctx *ctx, const uint8_t *src_dev, int64_t stride_img_bytes, int64_t stride_row_bytes, int32_t channels /*1 | 3*/,
+                            int32_t n, int32_t src_rows, int32_t src_cols, int32_t rows, int32_t cols, const rcn_img_options *opt,
+                            uint8_t *rgb_out_dev, uint8_t *gray_out_dev);
+/* rgba_out[i][k] = (r, g, b, 0) of rgb[i][y][x] at xy_int[i][k] = (x, y) for k < min(counts[i], K); zero bytes for the other
+ * rows and for coordinates outside the image (the reference's unchecked at<> is undefined there). */
+int  rcn_feat_colors_device(rcn_ctx *ctx, const uint8_t *rgb_dev /*[n][rows][cols][3]*/, int32_t n, int32_t rows, int32_t cols,
+                            const int32_t *xy_int_dev /*[n][K][2]*/, const int32_t *counts_dev /*[n]*/, int32_t K, uint8_t *rgba_out_dev /*[n][K][4]*/);
+/* rgba_out[l] = feat_rgba[first_img[l]][first_feat[l]]; zero bytes when either index is out of range */
+int  rcn_landmark_colors_device(rcn_ctx *ctx, const uint8_t *feat_rgba_dev /*[n][K][4]*/, int32_t n, int32_t K, int32_t L,
+                                const int32_t *first_img_dev, const int32_t *first_feat_dev, uint8_t *rgba_out_dev /*[L][4]*/);
+/* Utils::saveCloud's vertices, 16-byte records (float x, y, z; uint8 r, g, b, a = 255).  inlier_dev != NULL (the flags of
+ * rcn_ba_session_validity, uploaded by the caller): the L landmarks with every outlier painted (253, 0, 0), the same L landmarks
+ * in their own colours, then one vertex per camera at -R^T t (fp64, each component one ascending sum of rounded products),
+ * coloured (0, 250, 0), in the caller's order; NULL: the landmarks, then the cameras.  xyz_dev: what
+ * rcn_ba_session_points_device returns.  *n_vertices_out (host): 2 L + C or L + C, written before the call returns. */
+int  rcn_cloud_vertices_device(rcn_ctx *ctx, const double *xyz_dev /*[L][3]*/, const uint8_t *lm_rgba_dev /*[L][4]*/, const uint8_t *inlier_dev,
+                               int32_t L, const double *poses34_dev /*[C][12]*/, int32_t C, void *vertices_out_dev, int64_t *n_vertices_out);
+/* Host code: a PLY file of those records (property float x / y / z, uchar red / green / blue / alpha), ASCII or
+ * binary_little_endian.  RCN_ERR_IO when the file cannot be written. */
+int  rcn_cloud_write_ply(const char *path, const void *vertices_host, int64_t n_vertices, int32_t binary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,8 @@ SYMBOLS = [
     "rcn_sift_describe_device", "rcn_sift_detect_and_compute_device",
     "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
+    "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
+    "rcn_feat_colors_device", "rcn_landmark_colors_device", "rcn_cloud_vertices_device", "rcn_cloud_write_ply",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -130,6 +132,10 @@ class SiftLayout(C.Structure):
                 ("base_sigma", C.c_double), ("oct_h", C.c_int32 * 16), ("oct_w", C.c_int32 * 16),
                 ("layer_sigma", C.c_double * 8), ("layer_taps", C.c_int32 * 8), ("layer_offset", (C.c_int64 * 8) * 16),
                 ("floats_per_image", C.c_int64)]
+
+
+class ImgOptions(C.Structure):
+    _fields_ = [("order", C.c_int32), ("gray_bits", C.c_int32)]
 
 
 class RetrOptions(C.Structure):
@@ -255,6 +261,24 @@ def load():
     L.rcn_sift_layout.argtypes = [i32, i32, C.POINTER(SiftOptions), C.POINTER(SiftLayout)]
     L.rcn_sift_set_chunk_images.restype = C.c_int
     L.rcn_sift_set_chunk_images.argtypes = [vp, i32]
+    L.rcn_img_reshape_size.restype = C.c_int
+    L.rcn_img_reshape_size.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]
+    L.rcn_img_resize_tables.restype = C.c_int
+    L.rcn_img_resize_tables.argtypes = [i32, i32, i32, vp, vp, C.POINTER(i32)]
+    L.rcn_img_default_options.restype = None
+    L.rcn_img_default_options.argtypes = [C.POINTER(ImgOptions)]
+    L.rcn_img_prepare_plan.restype = C.c_int
+    L.rcn_img_prepare_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.rcn_img_prepare_device.restype = C.c_int
+    L.rcn_img_prepare_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, C.POINTER(ImgOptions), vp, vp]
+    L.rcn_feat_colors_device.restype = C.c_int
+    L.rcn_feat_colors_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp]
+    L.rcn_landmark_colors_device.restype = C.c_int
+    L.rcn_landmark_colors_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    L.rcn_cloud_vertices_device.restype = C.c_int
+    L.rcn_cloud_vertices_device.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, C.POINTER(i64)]
+    L.rcn_cloud_write_ply.restype = C.c_int
+    L.rcn_cloud_write_ply.argtypes = [C.c_char_p, vp, i64, i32]
     sift_img = [vp, vp, i32, i64, i64, i64, i32, i32, i32, C.POINTER(SiftOptions)]     # ctx, images, dtype, strides, n H W, options
     sift_kp = [vp, vp, vp, vp, vp, vp, vp]                                              # xy, xy_int, size, angle, response, octave, counts
     L.rcn_sift_pyramid_device.restype = C.c_int

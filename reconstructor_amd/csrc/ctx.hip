@@ -92,7 +92,7 @@ void rcn_destroy(rcn_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     rcn_match_release(ctx);
     DevBuf *bufs[] = {&ctx->img_table, &ctx->pairs_dev, &ctx->groups_dev, &ctx->cand, &ctx->owner,
-                      &ctx->fb_list, &ctx->sv_list, &ctx->counters, &ctx->out_tmp, &ctx->cnt_tmp, &ctx->scale_dev, &ctx->desc_bad, &ctx->kp_ws, &ctx->sg_ws, &ctx->sg_scores, &ctx->gnn_ws, &ctx->gnn_mdesc, &ctx->sp_ws, &ctx->sp_out, &ctx->sift_ws, &ctx->sift_pyr, &ctx->retr_ws, &ctx->retr_out};
+                      &ctx->fb_list, &ctx->sv_list, &ctx->counters, &ctx->out_tmp, &ctx->cnt_tmp, &ctx->scale_dev, &ctx->desc_bad, &ctx->kp_ws, &ctx->sg_ws, &ctx->sg_scores, &ctx->gnn_ws, &ctx->gnn_mdesc, &ctx->sp_ws, &ctx->sp_out, &ctx->sift_ws, &ctx->sift_pyr, &ctx->retr_ws, &ctx->retr_out, &ctx->img_ws};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : ctx->ba_ws) b.release();
     ctx->lm_ws.release();
@@ -107,6 +107,7 @@ void rcn_destroy(rcn_ctx *ctx)
     if (ctx->corr_ev) (void)hipEventDestroy(ctx->corr_ev);
     ctx->lid.release(); ctx->lid_slot_off.release(); ctx->lid_hws.release(); ctx->nvt_ws.release();
     if (ctx->nvt_ev) (void)hipEventDestroy(ctx->nvt_ev);
+    if (ctx->img_ev) (void)hipEventDestroy(ctx->img_ev);
     ctx->pnp_hws.release(); ctx->pnp_slots.release();
     ctx->tv_hws.release(); ctx->tv_dws.release(); ctx->tv_fws.release();
     if (ctx->tv_ev) (void)hipEventDestroy(ctx->tv_ev);

@@ -164,6 +164,10 @@ struct rcn_ctx {
     DevBuf sift_ws, sift_pyr; // sift.hip: candidate / keypoint lists and counters of one chunk of images; the pyramids of rcn_sift_detect_and_compute_device
     int32_t sift_chunk_images = 0;  // images per chunk of the SIFT detector (rcn_sift_set_chunk_images; 0: as many as fit the default cap)
     DevBuf retr_ws, retr_out; // retrieval.hip: assignments, segment sums and counts, the pair mask; global descriptors, similarities and lists of rcn_retr_image_pairs
+    DevBuf img_ws;            // imgprep.hip: the resize tables of one call, 8 bytes per output column and row
+    std::vector<char> img_stage_host;   // staging of those tables (uploaded asynchronously; img_ev marks the copy)
+    hipEvent_t img_ev = nullptr;
+    bool img_stage_pending = false;
     ScaleDev scale_host;     // staging of the host-fixed scale (uploaded asynchronously)
     bool scale_on_device = false;   // the last scale was fixed by k_fix_scale: scale / bias / max_norm above are stale until resolved
     bool want_dev_scale = false;    // shard.hip: fix the next scale on the device (no host read of the statistics)

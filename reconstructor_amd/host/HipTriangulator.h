@@ -3,8 +3,9 @@
 // containers, with the triangulation itself handed to rcn_triangulate (include/rcn.h) as ONE batch per call.
 // In the reference these are private members working on `features`, `landmarks`, `imgIdx2camPose`,
 // `imgIdx2camIntrinsics`, `registeredImages`, `imgMatches`, `featureMatches`; here the same containers are passed in.
-// Pose matrices: anything indexable as M(r,c).  Landmark colour and initialLandmark are not carried (rcn_types.h has
-// neither).
+// Pose matrices: anything indexable as M(r,c).  An accepted landmark takes the colour of the first entry of its track
+// (:429-433), read from the caller's features: zero when they carry none (HipImagePrep.h's extractFeatureColors fills
+// them).  initialLandmark is not carried (rcn_types.h does not have it).
 //
 // Why one batch gives the reference's result:
 //   - triangulateInitialPair triangulates every match of the pair: nothing depends on an earlier call.
@@ -102,6 +103,7 @@ public:
         for (size_t j = 0; j < batch.size(); ++j) {
             if (status[j] != 0) continue;
             Landmark lm(X[3 * j], X[3 * j + 1], X[3 * j + 2]);
+            if (!batch[j].empty()) colourOf(lm, *features.at(batch[j].front().first).at(batch[j].front().second));
             for (const auto &[imgIdx, featIdx] : batch[j]) {
                 lm.triangulatedFeatures.emplace_back(imgIdx, featIdx);
                 features.at(imgIdx).at(featIdx)->landmarkId = (int)landmarks.size();      // :481-487
@@ -293,6 +295,7 @@ public:
             if (st[j] != 0) continue;
             Landmark lm(X[3 * (size_t)j], X[3 * (size_t)j + 1], X[3 * (size_t)j + 2]);
             const int regImgIdx = src[3 * (size_t)j], regFeat = src[3 * (size_t)j + 1], featIdx = src[3 * (size_t)j + 2];
+            colourOf(lm, *features.at(regImgIdx).at(regFeat));
             lm.triangulatedFeatures.emplace_back(regImgIdx, regFeat);                       // matchedImgIdFeatId order, :543-544
             lm.triangulatedFeatures.emplace_back(imgIdx, featIdx);
             features.at(regImgIdx).at(regFeat)->landmarkId = (int)landmarks.size();          // :481-487; the table holds the same
@@ -300,6 +303,12 @@ public:
             landmarks.push_back(std::move(lm));
         }
         return std::vector<uint8_t>(st, st + nTracks);
+    }
+
+    // :429-433: a landmark is coloured by the first feature of its track
+    static void colourOf(Landmark &lm, const Feature<> &first)
+    {
+        lm.red = first.featColor.red; lm.green = first.featColor.green; lm.blue = first.featColor.blue;
     }
 
     // getLandmarkLocalCoords + calcProjectionError (:842-867) in the operation order of the device kernels (camgeom.h)

@@ -2,11 +2,12 @@
 //
 // Same names and member names as the reference (namespace reconstructor::Core) so that the
 // adapters below read like the reference's own call sites:
-//   FeatCoord / FeatDesc / Feature / FeaturePtr   datatypes.h:10-107
+//   FeatCoord / FeatDesc / FeatColor / Feature / FeaturePtr   datatypes.h:10-107
 //   FeatCoordConf / FeatureConf                   datatypes.h:30-44, 112-136 (SuperPoint: a confidence per keypoint)
 //   TriangulatedFeature / Landmark                datatypes.h:125-183
 //   PinholeCamera                                 Camera.h:12-120 (fX,fY,cX,cY,k1,k2 + project)
 //   GreyImage                                     the cv::Mat a FeatureDetector takes (FeatureDetector.h:28-31): one grey image
+//   ColourImage                                   the cv::Mat Utils::readImg fills (utils.cpp:100-109): interleaved 8-bit pixels
 //   ImageMatcher                                  ImageMatcher.h:14-22: the plugin that decides which image pairs are matched
 // Only the members the matcher / bundle-adjuster boundary touches are declared.
 #pragma once
@@ -39,11 +40,18 @@ struct FeatDesc {
     std::vector<float> desc;   // 128 (SIFT) / 32 (ORB as float) / 256 (SuperPoint) floats
 };
 
+struct FeatColor {
+    FeatColor() = default;
+    FeatColor(int red_, int green_, int blue_) : red(red_), green(green_), blue(blue_) {}
+    int red = 0, green = 0, blue = 0;
+};
+
 template <typename coordType = int> struct Feature {
     Feature() = default;
     Feature(FeatCoord<coordType> c, FeatDesc d) : featCoord(c), featDesc(std::move(d)) {}
     FeatCoord<coordType> featCoord;
     FeatDesc featDesc;
+    FeatColor featColor;       // the pixel under the feature (SequentialReconstructor.cpp:98-106); zero until extractFeatureColors fills it
     int landmarkId = -1;
 };
 template <typename coordType = int> using FeaturePtr = std::shared_ptr<Feature<coordType>>;
@@ -63,8 +71,10 @@ struct TriangulatedFeature {
 struct Landmark {
     Landmark() = default;
     Landmark(double x_, double y_, double z_) : x(x_), y(y_), z(z_) {}
+    Landmark(double x_, double y_, double z_, int red_, int green_, int blue_) : x(x_), y(y_), z(z_), red(red_), green(green_), blue(blue_) {}
     std::vector<TriangulatedFeature> triangulatedFeatures;
     double x = 0, y = 0, z = 0;
+    int red = 0, green = 0, blue = 0;      // the colour of the first feature of the track (:429-433)
 };
 
 // A grey image, row-major, standing in for cv::Mat where a detector takes one: bytes (the detector's input type) or floats on the 0..255 scale
@@ -73,6 +83,16 @@ struct GreyImage {
     bool isFloat = false;
     std::vector<uint8_t> u8;
     std::vector<float> f32;
+};
+
+// A decoded photograph standing in for the cv::Mat of Utils::readImg: `channels` interleaved bytes per pixel, rows `step` bytes
+// apart (cv::Mat::step: padding allowed; 0 = dense)
+struct ColourImage {
+    int rows = 0, cols = 0, channels = 3;
+    size_t step = 0;
+    std::vector<uint8_t> data;
+    size_t rowBytes() const { return step ? step : (size_t)cols * channels; }
+    const uint8_t *at(int y, int x) const { return data.data() + (size_t)y * rowBytes() + (size_t)x * channels; }
 };
 
 // Which images are matched against which: imgMatches[id] lists the partners of image id (the reference ships FakeImgMatcher, every
