@@ -565,27 +565,56 @@ __global__ void k_ba_diag(BaDev d, int what, double lo, double hi, int jacobi)
     }
 }
 
+// Double-double arithmetic for the landmarks' 3 x 3 inverses (error-free sums and, through the fused multiply-add, products: Dekker /
+// Knuth; Hida, Li, Bailey, "Algorithms for quad-double precision floating point arithmetic").  A landmark seen by two cameras has a
+// badly conditioned V: det and the cofactors are differences of products that cancel three to four digits, and in plain FP64 every
+// rounding of V, of a product or of a difference comes back multiplied by that factor -- up to 4e-13 of the block where the format
+// gives 1e-16.  Carried in double-double from the FP64 inputs to the one final rounding, the inverse is the
+// correctly rounded inverse of what the kernel was given.  About 300 additions and 70 FMAs per landmark and iteration, a dependent chain
+// in a launch of one thread per landmark: 1 ... 4 us of an iteration, 0.3 ... 0.7 % at cfg 4 and below, inside the spread of the solves
+// of one process.
+// (every operation below must be the rounded FP64 operation it is written as: a product contracted into the sum that uses it makes that
+//  sum more accurate and the error term computed behind it wrong -- measured: with the default contraction the inverses came out no
+//  better than plain FP64)
+#define DD_EXACT _Pragma("clang fp contract(off)")
+struct dd { double h, l; };
+__device__ __forceinline__ dd dd_fast_sum(double a, double b) { DD_EXACT const double s = a + b; return {s, b - (s - a)}; }      // |a| >= |b|
+__device__ __forceinline__ dd dd_two_sum(double a, double b) { DD_EXACT const double s = a + b, bb = s - a; return {s, (a - (s - bb)) + (b - bb)}; }
+__device__ __forceinline__ dd dd_two_prod(double a, double b) { DD_EXACT const double p = a * b; return {p, __builtin_fma(a, b, -p)}; }
+__device__ __forceinline__ dd dd_add(dd a, dd b) { DD_EXACT const dd s = dd_two_sum(a.h, b.h); return dd_fast_sum(s.h, s.l + (a.l + b.l)); }
+__device__ __forceinline__ dd dd_sub(dd a, dd b) { return dd_add(a, dd{-b.h, -b.l}); }
+__device__ __forceinline__ dd dd_mul(dd a, dd b) { DD_EXACT const dd p = dd_two_prod(a.h, b.h); return dd_fast_sum(p.h, p.l + (a.h * b.l + a.l * b.h)); }
+__device__ __forceinline__ dd dd_mul_d(dd a, double b) { DD_EXACT const dd p = dd_two_prod(a.h, b); return dd_fast_sum(p.h, p.l + a.l * b); }
+// a / b rounded to FP64: two quotient digits
+__device__ __forceinline__ double dd_div(dd a, dd b)
+{
+    DD_EXACT
+    const double q1 = a.h / b.h;
+    const dd r = dd_sub(a, dd_mul_d(b, q1));
+    return q1 + r.h / b.h;
+}
+
 // per point: V = scaled Vraw + dgp/radius, V^-1, scaled g_p
 __device__ __forceinline__ void point_solve_body(const BaDev &d, int j, double inv_radius)
 {
-    double V[9];
-    const double *s = d.sp + 3 * (size_t)j;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) V[3 * a + b] = d.Vraw[9 * (size_t)j + 3 * a + b] * s[a] * s[b];
-    for (int a = 0; a < 3; ++a) V[4 * a] += d.dgp[3 * (size_t)j + a] * inv_radius;
-    const double a = V[0], b = V[1], c = V[2], e = V[4], f = V[5], g = V[8];
-    const double A = e * g - f * f, B = c * f - b * g, C = b * f - c * e;
-    const double det = a * A + b * B + c * C;
+    const double *s = d.sp + 3 * (size_t)j, *Vr = d.Vraw + 9 * (size_t)j, *dg = d.dgp + 3 * (size_t)j;
+    // the upper triangle of V (the raw block is symmetric: the same products in the same order on both sides)
+    auto entry = [&](int p, int q) {
+        dd v = dd_mul_d(dd_two_prod(Vr[3 * p + q], s[p]), s[q]);
+        return p == q ? dd_add(v, dd_two_prod(dg[p], inv_radius)) : v;
+    };
+    const dd a = entry(0, 0), b = entry(0, 1), c = entry(0, 2), e = entry(1, 1), f = entry(1, 2), g = entry(2, 2);
+    const dd A = dd_sub(dd_mul(e, g), dd_mul(f, f)), B = dd_sub(dd_mul(c, f), dd_mul(b, g)), C = dd_sub(dd_mul(b, f), dd_mul(c, e));
+    const dd det = dd_add(dd_add(dd_mul(a, A), dd_mul(b, B)), dd_mul(c, C));
     double Vi[9];
-    if (!(det > 0.0) || !isfinite(det)) {
+    if (!(det.h > 0.0) || !isfinite(det.h)) {
         d.flag[0] = 1;
         d.flag[1] = 1;      // (the trailing workgroups of the Schur diagonal launch clear the flag words BEHIND this kernel: they restore [0] from this word)
         for (int i = 0; i < 9; ++i) Vi[i] = 0.0;
     } else {
-        const double id = 1.0 / det;
-        Vi[0] = A * id; Vi[1] = B * id; Vi[2] = C * id;
-        Vi[3] = Vi[1]; Vi[4] = (a * g - c * c) * id; Vi[5] = (b * c - a * f) * id;
-        Vi[6] = Vi[2]; Vi[7] = Vi[5]; Vi[8] = (a * e - b * b) * id;
+        Vi[0] = dd_div(A, det); Vi[1] = dd_div(B, det); Vi[2] = dd_div(C, det);
+        Vi[3] = Vi[1]; Vi[4] = dd_div(dd_sub(dd_mul(a, g), dd_mul(c, c)), det); Vi[5] = dd_div(dd_sub(dd_mul(b, c), dd_mul(a, f)), det);
+        Vi[6] = Vi[2]; Vi[7] = Vi[5]; Vi[8] = dd_div(dd_sub(dd_mul(a, e), dd_mul(b, b)), det);
     }
     for (int i = 0; i < 9; ++i) d.Vinv[9 * (size_t)j + i] = Vi[i];
     for (int i = 0; i < 3; ++i) d.gps[3 * (size_t)j + i] = d.gpraw[3 * (size_t)j + i] * s[i];
@@ -1532,11 +1561,20 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     const bool pairs_build = gather && np > 0 && !pairs_cached;
     // (queued BEHIND the first evaluation's launches, below: on these sizes the host's enqueue rate is what the device waits for, and the
     //  evaluation is what the host waits for first)
+    // (what was launched, for the probe's record: 0 lists reused / nothing, 1 k_pair_small, 2 count, scan and fill; 1 k_ba_schur_mfma<4>, 2 the
+    //  workgroup form; the gather depth of the diagonal kernel)
+    int pair_path = 0, offdiag_kernel = 0, diag_smb = 0;
+    BaProbe *const probe = ctx->ba_probe;
+    auto grab = [&](auto &vec, const void *src, size_t count) -> hipError_t {      // (probe only; the stream has been synchronised)
+        vec.resize(count);
+        return count ? hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
+    };
     auto build_pairs = [&]() -> int {
         hipStream_t sp = rcn_chol_idle_stream(ctx);          // the factorisation's panel stream, idle: the stream was synchronised above and every factorisation joins its streams
         int *const long_keys = pk_cnt, *const long_count = pk_fill + nkeys;      // (the counts are dead once the lists are filled; a spare word behind the fill cursors)
-        if (ctx->ba_pair_small && nkeys <= 1024 && npairs_lower <= 16384) k_pair_small<<<1, 1024, 0, sp>>>(d, pk_off, pk_list, nkeys, long_count);      // (the smallest of the reference's own sizes: one launch for six; beyond, one workgroup walks the pairs slower than six launches)
+        if (ctx->ba_pair_small && nkeys <= 1024 && npairs_lower <= 16384) { k_pair_small<<<1, 1024, 0, sp>>>(d, pk_off, pk_list, nkeys, long_count); pair_path = 1; }      // (the smallest of the reference's own sizes: one launch for six; beyond, one workgroup walks the pairs slower than six launches)
         else {
+            pair_path = 2;
             RCN_HIP(hipMemsetAsync(pk, 0, sizeof(int) * (3 * (size_t)nkeys + 4 + (nkeys + 1023) / 1024), sp));
             const int thr = std::min(256, std::max(64, (kmax * kmax + 63) / 64 * 64));
             k_pair_count<<<np, thr, 0, sp>>>(d, pk_cnt);
@@ -1707,14 +1745,14 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
             if (!pairs_awaited) { RCN_HIP(hipStreamWaitEvent(st, ctx->ba_pair_ev, 0)); pairs_awaited = true; }
             if (nc > 1) {
                 const int nlow = nc * (nc - 1) / 2;
-                if (npairs_lower / (size_t)nlow > 128) k_ba_schur_mfma_wg<<<nlow, 512, 0, st>>>(d, pk_off, pk_list);   // long lists: a workgroup per block
-                else k_ba_schur_mfma<4><<<(nlow + 3) / 4, 256, 0, st>>>(d, pk_off, pk_list);
+                if (npairs_lower / (size_t)nlow > 128) { k_ba_schur_mfma_wg<<<nlow, 512, 0, st>>>(d, pk_off, pk_list); offdiag_kernel = 2; }   // long lists: a workgroup per block
+                else { k_ba_schur_mfma<4><<<(nlow + 3) / 4, 256, 0, st>>>(d, pk_off, pk_list); offdiag_kernel = 1; }
             }
             // (fused_finish: the padded rows, the right-hand-side row and the flag words ride in the same launch)
             const int fin = fused_finish ? (chain ? 1 : 0) : -1;
             const int fin_blocks = fused_finish ? (int)(((size_t)(npad - n) * npad + 1023) / 1024) : 0;
-            if (nc < 128) k_ba_schur_diag_mfma<12><<<nc * csplit + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, csplit, fin);      // (few cameras: latency-bound, deep gathers)
-            else k_ba_schur_diag_mfma<4><<<nc + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, 1, fin);
+            if (nc < 128) { k_ba_schur_diag_mfma<12><<<nc * csplit + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, csplit, fin); diag_smb = 12; }      // (few cameras: latency-bound, deep gathers)
+            else { k_ba_schur_diag_mfma<4><<<nc + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, 1, fin); diag_smb = 4; }
             if (!fused_finish && npad > n) k_ba_S_pad<<<(npad - n + 127) / 128, 128, 0, st>>>(d);
         } else {
             if (np > 0) k_ba_schur<<<np, std::min(256, std::max(64, 64 * ((kmax * kmax + 7) / 8))), 0, st>>>(d, Sb);
@@ -1724,6 +1762,29 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         if (rhs_row && !fused_finish) k_ba_S_rhs_row<<<(n + 1 + 255) / 256, 256, 0, st>>>(d);
         RCN_HIP(hipGetLastError());
         if (phase_times) RCN_HIP(hipEventRecord(ctx->ba_tev[1], st));
+        if (probe && iter == probe->iteration) {
+            // capture A: everything the step has built stands in HBM; the factorisation below overwrites the reduced system
+            BaProbe &q = *probe;
+            RCN_HIP(hipStreamSynchronize(st));
+            q.n = n; q.npad = npad; q.csplit = csplit; q.offdiag_kernel = offdiag_kernel; q.diag_smb = diag_smb; q.pair_path = pair_path;
+            q.fin = (gather && fused_finish) ? (chain ? 1 : 0) : -1; q.rhs_row = rhs_row; q.fused_finish = fused_finish; q.chain = chain; q.radius = radius;
+            RCN_HIP(grab(q.J, d.J, JROW * (size_t)no)); RCN_HIP(grab(q.crot, d.crot, CROT * (size_t)nc));
+            RCN_HIP(grab(q.Uraw, d.Uraw, 100 * (size_t)nc)); RCN_HIP(grab(q.gcraw, d.gcraw, 10 * (size_t)nc));
+            RCN_HIP(grab(q.Vraw, d.Vraw, 9 * (size_t)np)); RCN_HIP(grab(q.gpraw, d.gpraw, 3 * (size_t)np));
+            RCN_HIP(grab(q.sc, d.sc, (size_t)n)); RCN_HIP(grab(q.sp, d.sp, 3 * (size_t)np));
+            RCN_HIP(grab(q.dgc, d.dgc, (size_t)n)); RCN_HIP(grab(q.dgp, d.dgp, 3 * (size_t)np));
+            RCN_HIP(grab(q.Vinv, d.Vinv, 9 * (size_t)np)); RCN_HIP(grab(q.gps, d.gps, 3 * (size_t)np));
+            RCN_HIP(grab(q.WY, d.WY, 2 * WROW * (size_t)no));
+            RCN_HIP(grab(q.S, d.S, (size_t)npad * npad)); RCN_HIP(grab(q.rhs, d.rhs, (size_t)npad));
+            RCN_HIP(grab(q.flag, d.flag, 24)); RCN_HIP(grab(q.tickets, d.tickets, 2 * (size_t)nc));
+            RCN_HIP(grab(q.cam_off, d.cam_off, (size_t)nc + 1)); RCN_HIP(grab(q.cam_dim, d.cam_dim, (size_t)nc)); RCN_HIP(grab(q.cols, d.cols, 10 * (size_t)nc));
+            q.pk_off.clear(); q.pk_list.clear();
+            if (gather && np > 0) {
+                RCN_HIP(grab(q.pk_off, pk_off, (size_t)nkeys + 1));
+                RCN_HIP(grab(q.pk_list, pk_list, std::min((size_t)std::max(q.pk_off[nkeys], 0), npairs_lower)));      // (never past the allocation, whatever the total says)
+            }
+            q.got_a = 1;
+        }
         // Dense Cholesky of the padded system and the triangular solves behind it (chol.h).  A hand-off between its streams that times out raises flag 3, read
         // below with the step's scalars: the factorisation is then repeated on ONE stream, and every later one runs that way (ctx->chol.safe).  Same bits either way.
         const CholSystem sys = {d.S, d.L, d.Linv, SI, d.flag, d.rhs, d.yc, n, npad, nblk, rhs_row, chain, fused_finish};
@@ -1781,7 +1842,22 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         reuse_diag = true;
         const double model_change = hs[2];
         const bool solve_ok = hflag == 0 && hs[9] == 0.0 && std::isfinite(model_change);
+        // capture B (probe only): what the step has left behind its candidate's evaluation; the solve ends with it
+        auto capture_b = [&](int how) -> int {
+            BaProbe &q = *probe;
+            RCN_HIP(hipStreamSynchronize(st));
+            RCN_HIP(grab(q.x, d.rhs, (size_t)npad)); RCN_HIP(grab(q.tobs, d.tobs, 3 * (size_t)no));
+            RCN_HIP(grab(q.stc, d.stc, (size_t)n)); RCN_HIP(grab(q.stp, d.stp, 3 * (size_t)np));
+            RCN_HIP(grab(q.dlc, d.dlc, (size_t)n)); RCN_HIP(grab(q.dlp, d.dlp, 3 * (size_t)np));
+            RCN_HIP(grab(q.poses2, d.poses2, 6 * (size_t)nc)); RCN_HIP(grab(q.intr2, d.intr2, 6 * (size_t)nc)); RCN_HIP(grab(q.pts2, d.pts2, 3 * (size_t)np));
+            RCN_HIP(grab(q.crot2, d.crot2, CROT * (size_t)nc)); RCN_HIP(grab(q.scal, d.scal, 16));
+            RCN_HIP(grab(q.flag_b, d.flag, 24)); RCN_HIP(grab(q.tickets_b, d.tickets, 2 * (size_t)nc));      // (at rest again: every ticket word zero)
+            q.got_b = how;
+            return RCN_OK;
+        };
+        if (probe) { probe->log.insert(probe->log.end(), hs, hs + 14); probe->log.push_back(0.0); }
         if (!solve_ok || !(model_change > 0.0)) {
+            if (probe && iter == probe->iteration) { const int rcb = capture_b(2); if (rcb) return rcb; termination = RCN_BA_NO_CONVERGENCE; break; }
             sum->invalid_steps++;
             if (++invalid_run >= opt->max_consecutive_invalid_steps) { termination = RCN_BA_FAILURE; break; }      // Ceres' HandleInvalidStep: pre-increment, `>=` (see the oracle)
             radius /= decrease; decrease *= 2.0; reuse_diag = false;
@@ -1811,7 +1887,11 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
             for (int it = 0;;) {
                 cur = rcn_ls::Sample();
                 cur.x = a; cur.v = cand_cost; cur.v_ok = std::isfinite(cand_cost);
-                if (cur.v_ok && cur.v <= cost + 1e-4 * g0 * a) { found = true; break; }
+                if (cur.v_ok && cur.v <= cost + 1e-4 * g0 * a) {
+                    if (probe && iter == probe->iteration) probe->trials.insert(probe->trials.end(), {a, cand_cost, std::nan(""), dmax});
+                    found = true;
+                    break;
+                }
                 if (cur.v_ok) {
                     if (no > 0) k_ba_dirgrad<<<eb, 256, 0, st>>>(d, d.poses2, d.intr2, d.pts2, d.partial);
                     k_finish_sum<<<1, 256, 0, st>>>(d.partial, no > 0 ? eb : 0, d.scal + 10, 1.0);
@@ -1825,6 +1905,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
                 RCN_HIP(read_scal(12));
                 if (cur.v_ok) { cur.g = hs[10] / a; cur.g_ok = std::isfinite(cur.g); }
                 if (dmax < 0.0) dmax = hs[11] / a;
+                if (probe && iter == probe->iteration) probe->trials.insert(probe->trials.end(), {a, cand_cost, cur.g_ok ? cur.g : std::nan(""), dmax});
                 if (++it >= 20) break;
                 const double an = rcn_ls::next_step(start, prev, cur, 1e-3 * a, 0.6 * a);
                 if (an * dmax < 1e-9) break;
@@ -1835,7 +1916,9 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
                 RCN_HIP(trial(a));
             }
             if (!found && bt) RCN_HIP(trial(1.0));   // the search gave up: the full step stands
+            if (probe) probe->log.back() = (double)bt;
         }
+        if (probe && iter == probe->iteration) { const int rcb = capture_b(1); if (rcb) return rcb; termination = RCN_BA_NO_CONVERGENCE; break; }
         if (!std::isfinite(cand_cost)) cand_cost = DBL_MAX;
         if (std::sqrt(dn2) <= opt->parameter_tolerance * (std::sqrt(xn2) + opt->parameter_tolerance)) {
             termination = RCN_BA_CONVERGENCE_PARAMETER;

@@ -131,6 +131,31 @@ struct CorrLists {
     void release() { ent.release(); list_off.release(); dir.release(); id2slot.release(); ids.clear(); live = false; id_lo = id_span = 0; }
 };
 
+// What one Levenberg-Marquardt iteration of rcn_int_ba_solve leaves on the device, copied out at two points of that iteration
+// (tools/ba_step_check.hip, tests/test_ba_step_gpu.py).  Not part of the ABI: rcn_ctx::ba_probe is null wherever
+// the library creates a context, and the solve then pays a few host pointer tests per iteration.  Capture A is taken behind the Schur / finish
+// launches and in front of the factorisation (which destroys the reduced system), capture B behind the candidate's evaluation (and the line
+// search) and in front of the parameter-tolerance test (an accepted step overwrites the observation rows); the solve ends there.
+struct BaProbe {
+    int iteration = 1;                 // in: the iteration (1-based, as rcn_ba_summary counts) to capture
+    int got_a = 0, got_b = 0;          // out: the captures were taken; got_b = 2: the step was invalid (no candidate was judged)
+    // ---- A
+    int n = 0, npad = 0, csplit = 0, offdiag_kernel = 0, diag_smb = 0, fin = -2, rhs_row = 0, fused_finish = 0, chain = 0, pair_path = 0;
+    //   offdiag_kernel: 0 none, 1 k_ba_schur_mfma<4>, 2 k_ba_schur_mfma_wg; diag_smb: the SMB of k_ba_schur_diag_mfma; pair_path: 0 lists reused,
+    //   1 k_pair_small, 2 count / scan / fill
+    double radius = 0.0;
+    std::vector<double> J, crot, Uraw, gcraw, Vraw, gpraw, sc, sp, dgc, dgp, Vinv, gps, WY, S, rhs;
+    std::vector<int> flag, cam_off, cam_dim, cols, pk_off;      // flag: all 24 words (flag, reduction tickets, the factorisation's counters)
+    std::vector<unsigned> tickets;                              // the per-camera ticket words (2 nc)
+    std::vector<unsigned long long> pk_list;
+    // ---- B
+    std::vector<double> x, tobs, stc, stp, dlc, dlp, poses2, intr2, pts2, crot2, scal;      // x: the reduced solution as k_ba_backsub reads it; scal: 16 words
+    std::vector<int> flag_b;           // the same words as they stand behind the step
+    std::vector<unsigned> tickets_b;
+    std::vector<double> trials;        // per line-search trial of the iteration: alpha, candidate cost, directional derivative (NaN: not taken), |delta|_inf (-1: not yet)
+    std::vector<double> log;           // per iteration up to the captured one: scal[0 .. 14) as read behind the step, then the number of backtracks
+};
+
 struct rcn_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -265,6 +290,7 @@ struct rcn_ctx {
     uint64_t ba_pair_token = 0;         // whose pair lists the Schur-build workspace holds (0 = nobody's)
     std::vector<int> ba_pair_camdim;    // ... and the per-camera tangent dimensions they were built for (a camera without free parameters has no pairs)
     CholState chol;                     // the dense factorisation of the reduced system (chol.h, chol.hip)
+    BaProbe *ba_probe = nullptr;        // tools/ba_step_check.hip only: one LM iteration copied out (above)
     double *ba_host_scal = nullptr;   // pinned mirror of the LM step's scalars (16 doubles; [15]: sequence number), written by the step's last kernel
     unsigned long long ba_host_seq = 0;
     hipEvent_t ba_pair_ev;           // the pair lists of the Schur build are there

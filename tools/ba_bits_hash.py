@@ -1,5 +1,6 @@
 """tools/ba_bits_hash.py -- one SHA-256 over the results of five solves (cfg 5, cfg 4, 25 / 6 / 3 cameras): a change that must not move a bit prints the same line
-(round 5, before the change to k_ba_eval's staging: 8feb94621a42923c1bb83bda78219f55980d898d52a1b1a5eb975c2572cc8c3a)"""
+(round 5, before the change to k_ba_eval's staging: 8feb94621a42923c1bb83bda78219f55980d898d52a1b1a5eb975c2572cc8c3a; since the landmarks' 3 x 3 inverses are carried in
+double-double, DESIGN.md section 7.3: 52426048451eae305c35163f646227dd119fbe3f1991196d159dbc1d2c9b340b)"""
 import os, sys, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa
