@@ -609,7 +609,7 @@ __device__ __forceinline__ void point_solve_body(const BaDev &d, int j, double i
     double Vi[9];
     if (!(det.h > 0.0) || !isfinite(det.h)) {
         d.flag[0] = 1;
-        d.flag[1] = 1;      // (the trailing workgroups of the Schur diagonal launch clear the flag words BEHIND this kernel: they restore [0] from this word)
+        d.flag[1] = 1;      // (the trailing workgroups of the Schur diagonal launch -- k_ba_flag_reset where they do not run -- clear the flag words BEHIND this kernel: they restore [0] from this word)
         for (int i = 0; i < 9; ++i) Vi[i] = 0.0;
     } else {
         Vi[0] = dd_div(A, det); Vi[1] = dd_div(B, det); Vi[2] = dd_div(C, det);
@@ -1040,6 +1040,17 @@ __global__ __launch_bounds__(1024) void k_ba_schur_diag_mfma(BaDev d, const int 
             if (threadIdx.x == 0) __hip_atomic_store(d.tickets + d.nc + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+// The flag words of a step whose system is NOT finished by the launch above (fin < 0: n a multiple of the block, the forward substitution
+// as a launch of its own, the atomic Schur build): what its trailing workgroups do, as one small launch BEHIND the landmark blocks'
+// kernel -- [0] restored from the word that kernel raises for a singular block, [1] consumed, the factorisation's counters cleared.
+// (a host-side memset of the words stood here: it ran behind k_ba_gradmax's fused launch, which solves the blocks of the first step and of
+//  every step behind an accepted one, and wiped the flag of a singular block; the step then went on as a valid one)
+__global__ void k_ba_flag_reset(BaDev d)
+{
+    const int idx = threadIdx.x;
+    if (idx == 0) { const int ps = d.flag[1]; d.flag[1] = 0; d.flag[0] = ps ? 1 : 0; }
+    else if ((idx >= 2 && idx < 8) || (idx >= 12 && idx < 24)) d.flag[idx] = 0;
 }
 // padded rows of the dense system: identity (the gather form writes every other lower block itself)
 __global__ void k_ba_S_pad(BaDev d)
@@ -1732,14 +1743,13 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         const bool fused_finish = gather && rhs_row;
         const bool chain = rcn_chol_bwd_one_launch(ctx, nblk);      // backward substitution as one launch
         if (!fused_finish) {
-            RCN_HIP(hipMemsetAsync(d.flag, 0, 8 * sizeof(int), st));
-            RCN_HIP(hipMemsetAsync(d.flag + 12, 0, 12 * sizeof(int), st));
             if (!gather) RCN_HIP(hipMemsetAsync(Sb, 0, sizeof(double) * 100 * (size_t)nc * nc, st));
             if (npad > n) RCN_HIP(hipMemsetAsync(d.S + (size_t)n * npad, 0, sizeof(double) * (size_t)(npad - n) * npad, st));
             RCN_HIP(hipMemsetAsync(d.rhs, 0, sizeof(double) * npad, st));
         }
         if (np > 0 && !points_fresh) k_ba_point_solve<<<(np + 127) / 128, 128, 0, st>>>(d, ir);      // (a step behind an accepted one: done in k_ba_gradmax's launch)
         points_fresh = false;
+        if (!fused_finish) k_ba_flag_reset<<<1, 64, 0, st>>>(d);      // (behind the landmark blocks, whichever launch solved them: it consumes their word)
         if (no > 0) k_ba_wy<<<(unsigned)((10 * (size_t)no + 255) / 256), 256, 0, st>>>(d);
         if (gather) {
             if (!pairs_awaited) { RCN_HIP(hipStreamWaitEvent(st, ctx->ba_pair_ev, 0)); pairs_awaited = true; }

@@ -158,3 +158,35 @@ def make_always_invalid_scene(seed=7):
     sc["obs_cam"] = np.concatenate([sc["obs_cam"], [last, last]]).astype(np.int32)
     sc["obs_uv"] = np.concatenate([sc["obs_uv"], [[100.0, 90.0], [101.0, 91.0]]])
     return sc
+
+
+def _dead_camera_base(n_cams, dead, seed):
+    """make_scene(n_cams, 10 n_cams, obs_per_point=4) with camera `dead` given fx = fy = 0: its projection is the constant (cx, cy) and
+    every Jacobian entry of its observations is exactly zero.  Every landmark keeps at least three other observers."""
+    sc = dict(make_scene(n_cams, 10 * n_cams, obs_per_point=4, seed=seed))
+    intr = sc["intrinsics"].copy()
+    intr[dead, 0] = intr[dead, 1] = 0.0
+    sc["intrinsics"] = intr
+    return sc
+
+
+def make_lone_landmark_scene(n_cams, seed=7):
+    """ONE cause of an invalid LM step, exact in any floating-point arithmetic: a landmark block that is singular while the reduced camera
+    system is healthy.  Camera 0 has fx = fy = 0 and one appended landmark has two observations, both from camera 0: its 3 x 3 block is
+    exactly zero, and with min_lm_diagonal = 0 stays zero at any radius.  For intrinsics_mode = 0 and fix_cam0_pose = 1 camera 0 has no
+    free parameter and so no column in the reduced system: every camera block of S is an ordinary one."""
+    sc = _dead_camera_base(n_cams, 0, seed)
+    sc["points"] = np.concatenate([sc["points"], [[0.1, -0.2, 0.3]]])
+    j = sc["points"].shape[0] - 1
+    sc["obs_pt"] = np.concatenate([sc["obs_pt"], [j, j]]).astype(np.int32)
+    sc["obs_cam"] = np.concatenate([sc["obs_cam"], [0, 0]]).astype(np.int32)
+    sc["obs_uv"] = np.concatenate([sc["obs_uv"], [[100.0, 90.0], [101.0, 91.0]]])
+    return sc
+
+
+def make_dead_camera_scene(n_cams, dead, seed=7):
+    """The OTHER single cause: the reduced camera system breaks down while every landmark block is healthy.  The free camera `dead`
+    (>= 1) has fx = fy = 0 and there is no lone landmark: that camera's diagonal block of S is exactly zero with min_lm_diagonal = 0,
+    so a Cholesky pivot is not positive -- in the first block column for dead = 1, in the last for dead = n_cams - 1."""
+    assert 1 <= dead < n_cams
+    return _dead_camera_base(n_cams, dead, seed)

@@ -532,11 +532,14 @@ def write_scene(d, name, sc):
 
 
 def write_cases(d, cases):
-    """cases: dicts(name, scene, iteration, mode, fix0, fix1, jacobi, ub, radius)"""
+    """cases: dicts(name, scene, iteration, mode, fix0, fix1, jacobi, ub, radius[, lm]); lm: (min_lm_diagonal, max_lm_diagonal), absent or
+    None for the defaults -- the line then has no such columns"""
     with open(os.path.join(d, "cases.txt"), "w") as f:
-        f.write("# name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius\n")
+        f.write("# name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius [min_lm_diagonal max_lm_diagonal]\n")
         for c in cases:
-            f.write("%s %s %d %d %d %d %d %.17g %.17g\n" % (c["name"], c["scene"], c["iteration"], c["mode"], c["fix0"], c["fix1"], c["jacobi"], c["ub"], c["radius"]))
+            lm = c.get("lm")
+            f.write("%s %s %d %d %d %d %d %.17g %.17g%s\n" % (c["name"], c["scene"], c["iteration"], c["mode"], c["fix0"], c["fix1"], c["jacobi"], c["ub"], c["radius"],
+                                                          "" if lm is None else " %.17g %.17g" % tuple(lm)))
 
 
 _TYPES = dict(flag="<i4", flag_b="<i4", cam_off="<i4", cam_dim="<i4", cols="<i4", pk_off="<i4", tickets="<u4", tickets_b="<u4", pk_list="<u8")

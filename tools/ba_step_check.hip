@@ -6,8 +6,9 @@
 //   ba_step_check DIR
 //
 // DIR/cases.txt, one case per line (lines that start with # are skipped):
-//   name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius
-// (every other option as rcn_ba_default_options gives it for the scene's cameras; max_iterations at least `iteration`).
+//   name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius [min_lm_diagonal max_lm_diagonal]
+// (the last two columns are optional and come together: absent, both stay as rcn_ba_default_options gives them, like every other
+//  option; max_iterations at least `iteration`).
 // DIR/<scene>.dims ("n_cams n_points n_obs" as text), .poses .intr .pts .uv (float64, little-endian) and .ocam .opt (int32): several
 // cases may name one scene -- the pair lists of the second are then the reused ones, as in the product.
 // Writes DIR/<name>.meta ("key value" lines: what the probe recorded as integers, the summary's iteration count and termination) and
@@ -44,7 +45,7 @@ template <class T> static bool write_raw(const std::string &path, const std::vec
     return fclose(f) == 0 && put == v.size();
 }
 
-struct StepCase { std::string name, scene; int iteration, mode, fix0, fix1, jacobi; double ub, radius; };
+struct StepCase { std::string name, scene; int iteration, mode, fix0, fix1, jacobi; double ub, radius, lm_lo, lm_hi; bool lm_given; };
 struct StepScene { std::string name; int nc = 0, np = 0, no = 0; std::vector<double> poses, intr, pts, uv; std::vector<int> ocam, opt; };
 
 static int run(const std::string &dir)
@@ -62,6 +63,17 @@ static int run(const std::string &dir)
                 (c.mode != 0 && c.mode != 1)) {
                 fprintf(stderr, "cases.txt: cannot parse \"%s\"\n", line.c_str());
                 return 2;
+            }
+            // (optional trailing columns: both or neither, and nothing behind them)
+            c.lm_given = false;
+            std::string rest;
+            if (ls >> rest) {
+                std::istringstream lo(rest);
+                if (!(lo >> c.lm_lo) || !lo.eof() || !(ls >> c.lm_hi) || (ls >> rest) || !(c.lm_lo >= 0.0) || !(c.lm_hi >= c.lm_lo)) {
+                    fprintf(stderr, "cases.txt: cannot parse \"%s\"\n", line.c_str());
+                    return 2;
+                }
+                c.lm_given = true;
             }
             cases.push_back(c);
         }
@@ -107,6 +119,7 @@ static int run(const std::string &dir)
         rcn_ba_default_options(sc.nc, &o);
         o.intrinsics_mode = c.mode; o.fix_cam0_pose = c.fix0; o.fix_cam1_translation = c.fix1; o.jacobi_scaling = c.jacobi;
         o.focal_upper_bound = c.ub; o.initial_trust_region_radius = c.radius;
+        if (c.lm_given) { o.min_lm_diagonal = c.lm_lo; o.max_lm_diagonal = c.lm_hi; }
         o.max_iterations = std::max(o.max_iterations, c.iteration);
         BaProbe probe;
         probe.iteration = c.iteration;
