@@ -5,17 +5,23 @@
 //   cv::DescriptorMatcher::knnMatch(k=2) call site FeatureMatcher.cpp:49
 //   SequentialReconstructor::matchFeatures pair loop, SequentialReconstructor.cpp:199-279
 //
-// Pipeline per grid call:
-//   K1 k_coarse_top2   fp16 MFMA (v_mfma_f32_32x32x16_f16) distance tiles, running top-2 per
-//                      query with the train index packed into the low mantissa bits
-//   K2 k_rerank        exact fp64 re-computation of the two candidates in the canonical
-//                      order, certified against a rigorous bound on the coarse error;
-//                      rows that cannot be certified go to the fallback list
-//   K2b k_exact_rows   exact brute force of the listed rows (also the generic path)
-//   K3 k_unique_claim / k_unique_emit   lowest query index keeps a contested train row
+// Pipeline per grid call.  What is launched is decided on the host before the first launch and is data:
+// grid_plan.h (groups of pairs, pipeline chunks, order of the work items, workspace layout, which kernels).  Per chunk, in stream order:
+//   K1  k_coarse_top2 / k_coarse_top2_i8 (coarse_i8.h)   distance tiles on fp16 MFMA (16x16x32 at D = 256, 32x32x16 below) or int8 MFMA
+//                      (16x16x64), running top-2 per query with the train index packed into the key's low bits.  The host launches both
+//                      where the resident set admits int8; fix_scale chose one on the device and the other returns at once
+//       k_filter       certifies rows from the two keys alone against a rigorous bound on the coarse error; the rest go to the
+//                      survivor list or, where the coarse pass says nothing, to the fallback list
+//   K2  k_rerank_lds / k_rerank_generic   exact fp64 re-computation of the two candidates in the canonical order, certified against
+//                      the same bound; rows that cannot be certified go to the fallback list
+//       middle tier    k_mid_hist / bins / scatter / eval (+ k_mid_eval_i8, mid_i8.h) / exact: the fallback rows binned by train image,
+//                      a handful of candidates per row under a threshold, the canonical chain on those.  On a grid of several chunks
+//                      the rows are deferred (k_mid_defer) and the tier runs ONCE, behind the last chunk
+//   K2b k_exact_rows_lds / k_exact_rows   exact brute force of the rows the tier passes on (and of every row without the tier)
+//   K3  k_unique_pair, or k_unique_claim / k_unique_emit   lowest query index keeps a contested train row
 // The result is bit-identical to the canonical exact matcher whatever the coarse pass does:
 // the coarse pass only ever *proposes*.
-#include "rcn_internal.h"
+#include "rcn_internal.h"      // (with grid_plan.h: RCN_QT, RCN_GROUP, RCN_I8_IDX_BITS, RCN_MIDCAP, RCN_UNIQ_LDS, MI8_TILES)
 
 #include <algorithm>
 #include <cmath>
@@ -25,8 +31,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#define RCN_QT 512          // query rows per workgroup (8 waves x 64)
-#define RCN_GROUP 4         // consecutive pairs (same query image) swept by one workgroup
 #define RCN_TBL_BYTES ((RCN_GROUP * 24 + 127) / 128 * 128)   // LDS table of the group's train-image records
 #define RCN_NBUF 4          // LDS ring depth (train tiles)
 #define RCN_PD 2            // prefetch distance, tiles
@@ -36,7 +40,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define RCN_BT 64           // train rows per LDS tile (k_coarse_w4; k_coarse_top2: coarse_bt)
 #define RCN_PAD_HN 1.0e30f  // half-norm of padded train rows: never a candidate
 // int8 coarse pass (D padded to 256, Kp <= 4096; coarse_i8.h)
-#define RCN_I8_IDX_BITS 12                              // train-row bits of an int8 key
 #define RCN_I8_IDX_MASK ((1u << RCN_I8_IDX_BITS) - 1u)
 #define RCN_I8_PAD_ACC ((1 << (32 - RCN_I8_IDX_BITS)) - 1)   // accumulator of a padded train row: ranks last, fits the key
 #define RCN_I8_BT 128                                   // train rows per LDS tile
@@ -1342,7 +1345,6 @@ __global__ __launch_bounds__(64 * EX_WAVES) void k_exact_rows_lds(const ImgDev *
 // The candidates (a handful per row; the list holds RCN_MIDCAP) then go through the canonical fp64 chain and the
 // (value, index)-ordered top-2 of THOSE is the top-2 of all rows: same bits as K2b.  A list that overflows, and whatever
 // exceeds the tier's row budget, still goes to K2b.
-#define RCN_MIDCAP 32          // candidates kept per row
 #define RCN_MIDQ 32            // query rows per sweep of a train image (16 until the int8 coarse pass, which sends 50 times the rows here -- 1600 per train
                                // image and cfg-3 step -- so that sweeps are full either way: exact stages of a 32 640-pair launch 21.5 -> 19.2 ms)
 #define RCN_MIDROWS (1 << 21)  // rows per pipeline chunk the tier takes (the rest: K2b)
@@ -1862,7 +1864,6 @@ __global__ void k_unique_emit(const ImgDev *__restrict__ imgs, const int32_t *__
 // K3, one launch: a workgroup per pair with the owner table of the pair's train rows in LDS
 // (K2 <= 8192): claim with ds_min, emit, count -- the match table is read once and only the
 // entries that change are rewritten.
-#define RCN_UNIQ_LDS 8192
 __global__ __launch_bounds__(256) void k_unique_pair(const ImgDev *__restrict__ imgs, const int32_t *__restrict__ pairs,
                                                      int32_t *__restrict__ out, int64_t out_stride,
                                                      int32_t *__restrict__ counts, int pair_base)
@@ -2445,6 +2446,187 @@ template <int ABL, int SH> static hipError_t launch_coarse_i8(rcn_ctx *ctx, cons
     return hipGetLastError();
 }
 
+// The grid call's input to plan_grid (grid_plan.h), in ONE pass over the pair list: image ids -> table slots and row counts.
+static int fill_grid_shape(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs)
+{
+    grid::GridShape &gs = ctx->grid_shape;
+    // id -> image record through a flat table when the ids are small non-negative integers (they are image indices):
+    // a 500 000-pair list costs three million std::map walks otherwise, with the GPU idle behind the host
+    std::vector<const ImgHost *> flat;
+    {
+        int32_t lo = INT32_MAX, hi = INT32_MIN;
+        for (const auto &kv : ctx->images)
+            if (kv.first != INT32_MIN && kv.first != INT32_MIN + 1) { lo = std::min(lo, kv.first); hi = std::max(hi, kv.first); }
+        if (lo >= 0 && hi >= lo && hi < (1 << 24)) {
+            flat.assign((size_t)hi + 1, nullptr);
+            for (const auto &kv : ctx->images)
+                if (kv.first >= 0) flat[kv.first] = &kv.second;
+        }
+    }
+    auto lookup = [&](int32_t id) -> const ImgHost * {
+        if (!flat.empty() && id >= 0 && (size_t)id < flat.size()) return flat[id];
+        auto it = ctx->images.find(id);
+        return it == ctx->images.end() ? nullptr : &it->second;
+    };
+    gs.slots.resize(2 * (size_t)n_pairs); gs.k.resize((size_t)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        const ImgHost *a = lookup(pairs_host[2 * p]), *b = lookup(pairs_host[2 * p + 1]);
+        if (!a || !b) {
+            ctx->set_error("rcn_match_grid: image id not resident");
+            return RCN_ERR_NOT_FOUND;
+        }
+        gs.slots[2 * (size_t)p] = a->slot; gs.slots[2 * (size_t)p + 1] = b->slot;
+        gs.k[p] = {a->K, b->K, b->Kp};
+    }
+    gs.D = ctx->D; gs.DP = ctx->DP;
+    gs.n_slots = (int)ctx->table_host.size(); gs.n_cu = ctx->prop.multiProcessorCount;
+    gs.chunk_rows = ctx->chunk_rows; gs.mid_rows = ctx->mid_rows;
+    gs.i8_allowed = ctx->i8_allowed; gs.force_exact = ctx->force_exact; gs.no_item_order = ctx->no_item_order; gs.mid_i8_off = ctx->mid_i8_off;
+    return RCN_OK;
+}
+
+// K1 of one chunk: the fp16 kernel (or its one-wave form, diagnostic build) and, where the resident set admits it, the int8 kernel behind it.
+static int launch_coarse_stage(rcn_ctx *ctx, const grid::GridPlan &pl, const grid::Chunk &ck, const RerankArgs &ra, uint2 *cand_c)
+{
+    static_assert(sizeof(grid::Group) == sizeof(int2) && offsetof(grid::Group, count) == offsetof(int2, y), "the arranged groups are uploaded as int2");
+    CoarseArgs ca;
+    ca.imgs = ra.imgs; ca.pairs = ra.pairs; ca.cand = cand_c;
+    ca.groups = ctx->groups_dev.as<int2>() + ck.arr_off;
+    ca.n_groups = ck.arr_n; ca.tiles_per_pair = pl.tiles; ca.kq_stride = pl.kq_stride;
+    ca.items_per_xcd = ck.items_per_xcd;
+    ca.idx_mask = pl.idx_mask;
+    ca.sc = ra.sc;
+    const int blocks = ca.items_per_xcd * 8;
+    hipError_t e;
+    if (ctx->coarse_w4 && ctx->DP >= 64) {
+        switch (ctx->DP) {
+        case 64: e = launch_coarse_w4<64>(ctx, ca, blocks); break;
+        case 128: e = launch_coarse_w4<128>(ctx, ca, blocks); break;
+        default: e = launch_coarse_w4<256>(ctx, ca, blocks); break;
+        }
+    } else {
+        // MFMA shape: v_mfma_f32_16x16x32_f16 at D = 256 (+4 % by wall, A/B on one box: the chip holds a higher
+        // clock on it under this kernel's load), v_mfma_f32_32x32x16_f16 below (D = 128: -2.5 % on the other
+        // shape -- half the MFMA work per tile makes that kernel issue-bound, and 16x16x32 issues twice as many)
+        const int shape = ctx->coarse_shape >= 0 ? ctx->coarse_shape : (ctx->DP == 256 ? 1 : 0);
+        if (shape == 1) {
+            switch (ctx->DP) {
+            case 32: e = launch_coarse<32, 0, 1>(ctx, ca, blocks); break;
+            case 64: e = launch_coarse<64, 0, 1>(ctx, ca, blocks); break;
+            case 128: e = launch_coarse<128, 0, 1>(ctx, ca, blocks); break;
+            default:
+#ifdef RCN_DIAG
+                switch (ctx->ablate) {   // RCN_COARSE_ABL: timing experiments only (diagnostic build)
+                case 1: e = launch_coarse<256, 1, 1>(ctx, ca, blocks); break;
+                case 9: e = launch_coarse<256, 9, 1>(ctx, ca, blocks); break;
+                default: e = launch_coarse<256, 0, 1>(ctx, ca, blocks); break;
+                }
+#else
+                e = launch_coarse<256, 0, 1>(ctx, ca, blocks);
+#endif
+                break;
+            }
+        } else {
+            switch (ctx->DP) {
+            case 32:
+#ifdef RCN_DIAG
+                if (ctx->ablate == 1) { e = launch_coarse<32, 1, 0>(ctx, ca, blocks); break; }
+                if (ctx->ablate == 2) { e = launch_coarse<32, 2, 0>(ctx, ca, blocks); break; }
+                if (ctx->ablate == 6) { e = launch_coarse<32, 6, 0>(ctx, ca, blocks); break; }
+#endif
+                e = launch_coarse<32>(ctx, ca, blocks); break;
+            case 64: e = launch_coarse<64>(ctx, ca, blocks); break;
+            case 128:
+#ifdef RCN_DIAG
+                if (ctx->ablate == 1) { e = launch_coarse<128, 1, 0>(ctx, ca, blocks); break; }   // timing only: no top-2 fold
+                if (ctx->ablate == 2) { e = launch_coarse<128, 2, 0>(ctx, ca, blocks); break; }   // timing only: values-only fold
+                if (ctx->ablate == 6) { e = launch_coarse<128, 6, 0>(ctx, ca, blocks); break; }   // timing only: minimum-only fold (one operation per element)
+#endif
+                e = launch_coarse<128>(ctx, ca, blocks); break;
+            default: e = launch_coarse<256>(ctx, ca, blocks); break;
+            }
+        }
+    }
+    RCN_HIP(e);
+    // the int8 form of K1 (D padded to 256, at most 4096 padded rows per image): fix_scale chose between the two on the device, the
+    // host launches both and the one whose flag does not match returns at once.
+    // MFMA shape: v_mfma_i32_16x16x64_i8 (A/B on one box, EXPERIMENTS.md section 4: 108.0 ms per 32 640-pair launch against 117.8 ms on
+    // v_mfma_i32_32x32x32_i8 and 198.8 ms on the fp16 kernel)
+    if (ctx->i8_allowed) {
+#ifdef RCN_DIAG
+        if (ctx->coarse_i8_shape == 0) e = launch_coarse_i8<0, 0>(ctx, ca, blocks);
+        else if (ctx->ablate == 1) e = launch_coarse_i8<1, 1>(ctx, ca, blocks);      // timing only: no top-2 fold
+        else
+#endif
+        e = launch_coarse_i8<0, 1>(ctx, ca, blocks);
+        RCN_HIP(e);
+    }
+    return RCN_OK;
+}
+
+// What differs between the two passes of the middle tier: a chunk's own pass reads the chunk's candidate table and row list, the deferred
+// pass behind the last chunk the call's list of deferred rows, whose thresholds came with them.
+struct MidSource {
+    const uint2 *cand;
+    const unsigned long long *fb_list;
+    const unsigned *fb_count;
+    const float *thr_in;
+    const unsigned *tacc_in;
+    uint32_t midrows;
+};
+
+// One pass of the middle tier over src's rows, then K2b for what overflows the tier's candidate lists.  defer_rows (a chunk of a grid of
+// several): first the chunk's rows join the call's list if they fit (then ccnt[0] is 0 and the kernels behind find nothing to do).
+static int launch_mid_tier(rcn_ctx *ctx, const grid::GridPlan &pl, const RerankArgs &ra, unsigned *ccnt, const MidSource &src, bool defer_rows)
+{
+    const grid::MidLayout &mo = pl.mid_ws;
+    const int n_slots = ctx->grid_shape.n_slots, cus = ctx->prop.multiProcessorCount;
+    hipStream_t st = ctx->stream;
+    char *mw = ctx->mid_ws.as<char>();
+    MidArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.imgs = ra.imgs; ma.pairs = ra.pairs; ma.cand = src.cand; ma.fb_list = src.fb_list; ma.fb_count = src.fb_count;
+    ma.thr_in = src.thr_in; ma.tacc_in = src.tacc_in;
+    ma.sorted = (unsigned long long *)(mw + mo.sorted); ma.thr = (float *)(mw + mo.thr); ma.ccount = (unsigned *)(mw + mo.cc); ma.tacc = (unsigned *)(mw + mo.tacc);
+    ma.clist = (int32_t *)(mw + mo.cl); ma.fb2_list = (unsigned long long *)(mw + mo.fb2);
+    ma.hist = (unsigned *)(mw + mo.bins); ma.offs = ma.hist + (n_slots + 1); ma.cursor = ma.offs + (n_slots + 1); ma.ibase = ma.cursor + (n_slots + 1);
+    ma.n_items = ccnt + 3; ma.fb2_count = ccnt + 2;
+    ma.out = ra.out; ma.out_stride = ra.out_stride; ma.sc = ra.sc; ma.n_slots = n_slots; ma.kq_stride = pl.kq_stride; ma.D = ra.D;
+    ma.all_to_fallback = ra.all_to_fallback; ma.idx_mask = pl.idx_mask; ma.ratio = ra.ratio; ma.midrows = src.midrows;
+    if (defer_rows) {
+        k_mid_defer<<<cus * 2, 256, 0, st>>>(ma, (unsigned long long *)(mw + mo.def), (float *)(mw + mo.defthr), (unsigned *)(mw + mo.deftacc), ccnt, (unsigned)mo.rows_cap);
+        k_mid_defer_commit<<<1, 64, 0, st>>>(ccnt, (unsigned)mo.rows_cap);
+    }
+    k_mid_hist<<<cus * 4, 256, 0, st>>>(ma);
+    k_mid_bins<<<1, 1024, 0, st>>>(ma);
+    k_mid_scatter<<<cus * 4, 256, 0, st>>>(ma);
+    k_mid_eval<<<cus * 4, 256, 0, st>>>(ma);
+    if (pl.mid_i8) k_mid_eval_i8<<<dim3((unsigned)n_slots * MI8_TILES, (unsigned)pl.mid_i8_grid_y), 256, 0, st>>>(ma);
+    launch_mid_exact(ctx, ma, st);
+    RCN_HIP(hipGetLastError());
+    // K2b: the overflow list (the tier runs only where rows are read as float4)
+    k_exact_rows_lds<<<cus * 8, 64 * EX_WAVES, 0, st>>>(ra.imgs, ra.pairs, ma.fb2_list, ma.fb2_count, ra.D, ra.ratio, ra.out, ra.out_stride);
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
+
+// K3 for pairs p0 .. p0 + np - 1: one fused launch per pair where its owner table fits LDS, claim / emit through HBM otherwise; nothing
+// where the deferred pass follows (uniqueness then comes behind it, for every pair at once).
+static int launch_unique(rcn_ctx *ctx, const grid::GridPlan &pl, const RerankArgs &ra, int32_t *counts_dev, int p0, int np)
+{
+    hipStream_t st = ctx->stream;
+    if (pl.uniq_lds) {
+        if (!pl.defer) k_unique_pair<<<np, 256, 0, st>>>(ra.imgs, ra.pairs, ra.out, ra.out_stride, counts_dev, p0);
+    } else {
+        const int qblocks = (pl.kq_max + 255) / 256, eblocks = (int)((ra.out_stride + 255) / 256);
+        if (pl.kq_max > 0) k_unique_claim<<<dim3((unsigned)qblocks * (unsigned)np), 256, 0, st>>>(ra.imgs, ra.pairs, ra.out, ra.out_stride, ctx->owner.as<int32_t>(), pl.owner_stride, qblocks, p0);
+        RCN_HIP(hipGetLastError());
+        k_unique_emit<<<dim3((unsigned)eblocks * (unsigned)np), 256, 0, st>>>(ra.imgs, ra.pairs, ra.out, ra.out_stride, ctx->owner.as<int32_t>(), pl.owner_stride, counts_dev, eblocks, p0);
+    }
+    RCN_HIP(hipGetLastError());
+    return RCN_OK;
+}
+
 int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                            int32_t *out_dev, int64_t out_stride, int32_t *counts_dev)
 {
@@ -2472,135 +2654,38 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
     int rc = rcn_int_prepare_all(ctx);
     if (rc) return rc;
 
-    // image ids -> table slots; shape bookkeeping
-    std::vector<int32_t> &slots = ctx->slots_host;     // kept in the ctx: uploaded asynchronously
-    slots.assign(2 * (size_t)n_pairs, 0);
-    int kq_max = 0, kt_max = 0, ktp_max = 0;
-    int64_t rows = 0, pd = 0;
-    // id -> image record through a flat table when the ids are small non-negative integers (they are image indices):
-    // a 500 000-pair list costs three million std::map walks otherwise, with the GPU idle behind the host
-    std::vector<const ImgHost *> flat;
-    {
-        int32_t lo = INT32_MAX, hi = INT32_MIN;
-        for (const auto &kv : ctx->images)
-            if (kv.first != INT32_MIN && kv.first != INT32_MIN + 1) { lo = std::min(lo, kv.first); hi = std::max(hi, kv.first); }
-        if (lo >= 0 && hi >= lo && hi < (1 << 24)) {
-            flat.assign((size_t)hi + 1, nullptr);
-            for (const auto &kv : ctx->images)
-                if (kv.first >= 0) flat[kv.first] = &kv.second;
-        }
-    }
-    auto lookup = [&](int32_t id) -> const ImgHost * {
-        if (!flat.empty() && id >= 0 && (size_t)id < flat.size()) return flat[id];
-        auto it = ctx->images.find(id);
-        return it == ctx->images.end() ? nullptr : &it->second;
-    };
-    for (int p = 0; p < n_pairs; ++p) {
-        const ImgHost *a = lookup(pairs_host[2 * p]), *b = lookup(pairs_host[2 * p + 1]);
-        if (!a || !b) {
-            ctx->set_error("rcn_match_grid: image id not resident");
-            return RCN_ERR_NOT_FOUND;
-        }
-        slots[2 * p] = a->slot;
-        slots[2 * p + 1] = b->slot;
-        kq_max = std::max(kq_max, a->K);
-        kt_max = std::max(kt_max, b->K);
-        ktp_max = std::max(ktp_max, b->Kp);
-        rows += a->K;
-        pd += (int64_t)a->K * b->K;
-    }
-    if (out_stride < kq_max) {
+    // ---- the plan (grid_plan.h): groups, pipeline chunks, order of the work items, workspace layout, which kernels
+    if ((rc = fill_grid_shape(ctx, pairs_host, n_pairs))) return rc;
+    const grid::GridShape &gs = ctx->grid_shape;     // kept in the ctx with its plan: uploaded asynchronously
+    grid::GridPlan &pl = ctx->grid;
+    grid::plan_grid(gs, pl);
+    if (out_stride < pl.kq_max) {
         ctx->set_error("rcn_match_grid: out_stride smaller than a query image's K");
         return RCN_ERR_ARG;
     }
-    const int tiles = std::max(1, (kq_max + RCN_QT - 1) / RCN_QT);
-    const int kq_stride = tiles * RCN_QT;
-    int idx_bits = 1;
-    while ((1 << idx_bits) < ktp_max) ++idx_bits;
-    // The packed candidate keeps the train row in its low idx_bits and the accumulator's leading 32 - idx_bits bits
-    // above them: up to 16 index bits (65536 rows per image) leave sign + exponent + 7 mantissa bits, and the
-    // certificates price that quantum (k_filter: upper bounds are truncated value + one quantum), so a coarser
-    // value only sends more rows to the exact re-rank -- it never changes a result.
-    const bool mfma = ctx->DP != 0 && idx_bits <= 16 && !ctx->force_exact && kq_max > 0 && kt_max >= 2;
-    const uint32_t idx_mask = (1u << idx_bits) - 1u;
-    const int owner_stride = std::max(1, kt_max);
+    const grid::MidLayout &mo = pl.mid_ws;
+    const int n_chunks = (int)pl.chunks.size();
 
-    // groups: runs of consecutive pairs that share the query image, cut at RCN_GROUP
-    std::vector<int2> &groups = ctx->groups_host;
-    groups.clear();
-    for (int p = 0; p < n_pairs;) {
-        int cnt = 1;
-        while (p + cnt < n_pairs && cnt < RCN_GROUP && slots[2 * (p + cnt)] == slots[2 * p]) ++cnt;
-        groups.push_back(make_int2(p, cnt));
-        p += cnt;
-    }
-    const int n_groups = (int)groups.size();
-    // Pipeline chunks (round 4): the candidate table and the two row lists are sized for at most RCN_CHUNK_ROWS query-row slots
-    // and REUSED by consecutive ranges of the pair list, in stream order -- coarse(c), filter(c), re-rank(c), uniqueness(c),
-    // coarse(c+1), ...  Round 3 sized them for the whole grid: 16.4 GB each at cfg 3, three of them, and a 2000-image grid
-    // would not have fitted the device at all.  A chunk never exceeds the budget (the lists can therefore not overflow) and
-    // ends at a group boundary; a small grid is one chunk and runs exactly as before.  (The two-stream overlap of chunks that
-    // the diagnostic build once had measured slower in rounds 1 and 2 and is gone.)
-    std::vector<int> chunk_g0;      // first group of every chunk, then n_groups
-    int64_t cap_slots = 0, cap_rows = 0;
-    {
-        int64_t slots_c = 0, rows_c = 0;
-        chunk_g0.push_back(0);
-        for (int g = 0; g < n_groups; ++g) {
-            int64_t gs = (int64_t)groups[g].y * kq_stride, gr = 0;
-            for (int r = 0; r < groups[g].y; ++r) gr += lookup(pairs_host[2 * (groups[g].x + r)])->K;
-            if (slots_c > 0 && slots_c + gs > ctx->chunk_rows) {
-                chunk_g0.push_back(g);
-                cap_slots = std::max(cap_slots, slots_c); cap_rows = std::max(cap_rows, rows_c);
-                slots_c = 0; rows_c = 0;
-            }
-            slots_c += gs; rows_c += gr;
-        }
-        cap_slots = std::max(cap_slots, slots_c); cap_rows = std::max(cap_rows, rows_c);
-        chunk_g0.push_back(n_groups);
-    }
-    const int n_chunks = (int)chunk_g0.size() - 1;
-    const bool vec4 = (ctx->D % 4) == 0;
-    const bool mid = vec4 && kt_max >= 2;            // the middle tier reads rows as float4
-    const int n_slots = (int)ctx->table_host.size();
-
-    RCN_HIP(ctx->pairs_dev.reserve(slots.size() * sizeof(int32_t)));
-    RCN_HIP(ctx->cand.reserve((size_t)std::max<int64_t>(1, cap_slots) * sizeof(uint2)));
-    const bool uniq_lds = kt_max <= RCN_UNIQ_LDS;     // owner table of a pair fits LDS: one fused launch
-    if (!uniq_lds) RCN_HIP(ctx->owner.reserve((size_t)n_pairs * owner_stride * sizeof(int32_t)));
-    RCN_HIP(ctx->fb_list.reserve(std::max<int64_t>(1, cap_rows) * sizeof(unsigned long long)));
-    RCN_HIP(ctx->sv_list.reserve(std::max<int64_t>(1, cap_rows) * sizeof(unsigned long long)));
-    // middle tier: binned rows, thresholds, candidate lists, work items, the overflow list, three words per image slot
-    const size_t mid_rows_cap = (size_t)std::min<int64_t>(std::max<int64_t>(1, cap_rows), ctx->mid_rows);
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    // (the bins come FIRST: their place must not move with the row count of the grid, they carry state -- zeros -- from call to call)
-    const size_t mo_bins = 0, mo_sorted = mo_bins + al(4 * 4 * ((size_t)n_slots + 1)), mo_thr = mo_sorted + al(8 * mid_rows_cap), mo_cc = mo_thr + al(4 * mid_rows_cap),
-                 mo_cl = mo_cc + al(4 * mid_rows_cap), mo_fb2 = mo_cl + al(4 * mid_rows_cap * RCN_MIDCAP), mo_def = mo_fb2 + al(8 * mid_rows_cap),
-                 mo_defthr = mo_def + (n_chunks > 1 ? al(8 * mid_rows_cap) : 0), mo_deftacc = mo_defthr + (n_chunks > 1 ? al(4 * mid_rows_cap) : 0),
-                 mo_tacc = mo_deftacc + (n_chunks > 1 ? al(4 * mid_rows_cap) : 0), mo_fbtacc = mo_tacc + al(4 * mid_rows_cap),
-                 mo_end = mo_fbtacc + al(4 * (size_t)std::max<int64_t>(1, cap_rows));
-    // the int8 form of the tier's sweep (k_mid_eval_i8): launched beside k_mid_eval wherever the int8 K1 is; like it, it returns at once unless
-    // fix_scale chose the int8 path.  Its grid: (image slot x tile) x slabs of the bin's rows, the slabs so that a small grid still fills the chip
-    const bool mid_i8 = mid && mfma && ctx->i8_allowed && !ctx->mid_i8_off;
-    const dim3 mid_i8_grid((unsigned)n_slots * MI8_TILES,
-                           (unsigned)std::max<int64_t>(1, std::min<int64_t>(16, (4 * (int64_t)ctx->prop.multiProcessorCount) / std::max<int64_t>(1, (int64_t)n_slots * MI8_TILES))));
-    // the call's list of deferred rows (k_mid_defer): as many rows as one pass of the tier takes
-    const bool defer = mid && n_chunks > 1 && uniq_lds && kq_max > 0;
-#ifdef RCN_DIAG
-    ctx->diag_mid = {mid ? (size_t)1 : (size_t)0, mo_sorted, mo_tacc, mo_cc, mo_cl, mid_rows_cap};
-#endif
-    if (mid) {
-        const bool fresh = mo_end > ctx->mid_ws.cap;
-        RCN_HIP(ctx->mid_ws.reserve(mo_end));
-        if (fresh || ctx->mid_bins_slots != n_slots) {       // the bins are left zeroed by every pass (k_mid_bins); a new buffer, or another slot count, is not
-            RCN_HIP(hipMemsetAsync(ctx->mid_ws.as<char>() + mo_bins, 0, mo_sorted - mo_bins, ctx->stream));
-            ctx->mid_bins_slots = n_slots;
+    // ---- workspace and uploads
+    RCN_HIP(ctx->pairs_dev.reserve(gs.slots.size() * sizeof(int32_t)));
+    RCN_HIP(ctx->cand.reserve((size_t)std::max<int64_t>(1, pl.cap_slots) * sizeof(uint2)));
+    if (!pl.uniq_lds) RCN_HIP(ctx->owner.reserve((size_t)n_pairs * pl.owner_stride * sizeof(int32_t)));
+    RCN_HIP(ctx->fb_list.reserve(std::max<int64_t>(1, pl.cap_rows) * sizeof(unsigned long long)));
+    RCN_HIP(ctx->sv_list.reserve(std::max<int64_t>(1, pl.cap_rows) * sizeof(unsigned long long)));
+    if (pl.mid) {
+        const bool fresh = mo.end > ctx->mid_ws.cap;
+        RCN_HIP(ctx->mid_ws.reserve(mo.end));
+        if (fresh || ctx->mid_bins_slots != gs.n_slots) {       // the bins are left zeroed by every pass (k_mid_bins); a new buffer, or another slot count, is not
+            RCN_HIP(hipMemsetAsync(ctx->mid_ws.as<char>() + mo.bins, 0, mo.sorted - mo.bins, ctx->stream));
+            ctx->mid_bins_slots = gs.n_slots;
         }
     }
-    RCN_HIP(hipMemcpyAsync(ctx->pairs_dev.p, slots.data(), slots.size() * sizeof(int32_t),
+    RCN_HIP(hipMemcpyAsync(ctx->pairs_dev.p, gs.slots.data(), gs.slots.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice, ctx->stream));
-    if (!uniq_lds) RCN_HIP(hipMemsetAsync(ctx->owner.p, 0x7f, (size_t)n_pairs * owner_stride * sizeof(int32_t), ctx->stream));
+    if (!pl.uniq_lds) RCN_HIP(hipMemsetAsync(ctx->owner.p, 0x7f, (size_t)n_pairs * pl.owner_stride * sizeof(int32_t), ctx->stream));
     RCN_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pairs * sizeof(int32_t), ctx->stream));
+    RCN_HIP(ctx->groups_dev.reserve(std::max<size_t>(1, pl.arranged.size()) * sizeof(int2)));
+    RCN_HIP(hipMemcpyAsync(ctx->groups_dev.p, pl.arranged.data(), pl.arranged.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
 
     const ImgDev *imgs = ctx->img_table.as<ImgDev>();
     const int32_t *pairs = ctx->pairs_dev.as<int32_t>();
@@ -2612,240 +2697,77 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
     memset(&ra, 0, sizeof(ra));
     ra.imgs = imgs; ra.pairs = pairs;
     ra.out = out_dev; ra.out_stride = out_stride;
-    ra.n_pairs = n_pairs; ra.kq_stride = kq_stride; ra.D = ctx->D; ra.idx_mask = idx_mask;
+    ra.n_pairs = n_pairs; ra.kq_stride = pl.kq_stride; ra.D = ctx->D; ra.idx_mask = pl.idx_mask;
     ra.ratio = ratio;
     ra.sc = ctx->scale_dev.as<ScaleDev>();
-    ra.all_to_fallback = mfma ? 0 : 1;
+    ra.all_to_fallback = pl.mfma ? 0 : 1;
     ra.filter_pass = ctx->filter_pass ? 1 : 0; ra.rerank_pass = ctx->rerank_pass ? 1 : 0;
-    ra.fb_tacc = mid_i8 ? (unsigned *)(ctx->mid_ws.as<char>() + mo_fbtacc) : nullptr;
+    ra.fb_tacc = pl.mid_i8 ? (unsigned *)(ctx->mid_ws.as<char>() + mo.fbtacc) : nullptr;
 
-    // Order of the work items of a coarse launch: every XCD walks its own contiguous range of the chunk's
-    // group list, heaviest groups first, so that the last items to start are the short ones (the tail
-    // of a launch is one item long: 5 % of a cfg-2 grid for a four-pair group, 1 % for a one-pair group).
-    // Groups are dealt to the XCD ranges round-robin in descending weight; unused slots hold empty groups.
-    // (Measured and dropped in round 2: a train-block-major order -- every XCD runs the query tiles of ~8 query
-    // images against the SAME four train images at a time, so that all but one of them hit in its L2 -- is 0.5-1.5 %
-    // slower: the kernel is power-limited, not fabric-limited, and the order above has the shorter tail.)
-    std::vector<int> chunk_off((size_t)n_chunks, 0), chunk_ng((size_t)n_chunks, 0);
-    {
-        std::vector<int2> &arr = ctx->groups_arranged;
-        arr.clear();
-        std::vector<std::pair<int64_t, int>> order;
-        for (int c = 0; c < n_chunks; ++c) {
-            const int g0 = chunk_g0[c], g1 = chunk_g0[c + 1], ng = g1 - g0;
-            chunk_off[c] = (int)arr.size();
-            if (mfma && ng >= 64 && !ctx->no_item_order) {
-                order.resize((size_t)ng);
-                for (int g = 0; g < ng; ++g) {
-                    int64_t wgt = 0;
-                    for (int r = 0; r < groups[g0 + g].y; ++r) wgt += lookup(pairs_host[2 * (groups[g0 + g].x + r) + 1])->K;
-                    order[g] = std::make_pair(-wgt, g0 + g);
-                }
-                std::stable_sort(order.begin(), order.end());
-                const int gpx = (ng + 7) / 8;
-                const size_t base = arr.size();
-                arr.resize(base + (size_t)8 * gpx, make_int2(0, 0));
-                for (int k = 0; k < ng; ++k) arr[base + (size_t)(k % 8) * gpx + k / 8] = groups[order[k].second];
-                chunk_ng[c] = 8 * gpx;
-            } else {
-                arr.insert(arr.end(), groups.begin() + g0, groups.begin() + g1);
-                chunk_ng[c] = ng;
-            }
-        }
-        RCN_HIP(ctx->groups_dev.reserve(std::max<size_t>(1, arr.size()) * sizeof(int2)));
-        RCN_HIP(hipMemcpyAsync(ctx->groups_dev.p, arr.data(), arr.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-    }
     hipStream_t st = ctx->stream;
     // counters (words from +8): [0] fallback rows of the chunk, [1] survivors, [2] rows past the middle tier, [3] its work items;
     // [4..6] the same three summed over the chunks of the call (rcn_match_last_stats)
     unsigned *ccnt = ctx->counters.as<unsigned>() + 8;
     RCN_HIP(hipMemsetAsync(ccnt, 0, 8 * sizeof(unsigned), st));
     ctx->ev_chunks[evi] = 0;
+
+    // ---- the chunks, in stream order: coarse, filter, re-rank, middle tier and K2b, uniqueness
     for (int c = 0; c < n_chunks; ++c) {
-        const int g0 = chunk_g0[c], g1 = chunk_g0[c + 1];
-        if (g1 <= g0) continue;
-        const int p0 = groups[g0].x, p1 = g1 < n_groups ? groups[g1].x : n_pairs, np_c = p1 - p0;
+        const grid::Chunk &ck = pl.chunks[c];
+        const int p0 = ck.p0;
         // the chunk's candidates sit at the START of the buffer; the kernels index by grid-wide pair number
         // (indexed by grid-wide pair number: the chunk's table starts at pair p0.  The bias is applied to the ADDRESS -- a pointer in front
         //  of its allocation is not something C++ pointer arithmetic may form; the kernels only ever index pairs p0 .. p1 - 1 of it)
-        uint2 *cand_c = reinterpret_cast<uint2 *>(reinterpret_cast<uintptr_t>(ctx->cand.as<uint2>()) - (uintptr_t)((size_t)p0 * kq_stride * sizeof(uint2)));
+        uint2 *cand_c = reinterpret_cast<uint2 *>(reinterpret_cast<uintptr_t>(ctx->cand.as<uint2>()) - (uintptr_t)((size_t)p0 * pl.kq_stride * sizeof(uint2)));
         const bool tm = prof && c < RCN_EV_CHUNKS;
         if (tm) { RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][0], st)); ctx->ev_chunks[evi] = c + 1; }
-        if (mfma) {
-            CoarseArgs ca;
-            ca.imgs = imgs; ca.pairs = pairs; ca.cand = cand_c;
-            const int ng_c = chunk_ng[c];
-            ca.groups = ctx->groups_dev.as<int2>() + chunk_off[c];
-            ca.n_groups = ng_c; ca.tiles_per_pair = tiles; ca.kq_stride = kq_stride;
-            const int64_t items = (int64_t)ng_c * tiles;
-            ca.items_per_xcd = (int)((items + 7) / 8);
-            ca.idx_mask = idx_mask;
-            ca.sc = ctx->scale_dev.as<ScaleDev>();
-            const int blocks = ca.items_per_xcd * 8;
-            hipError_t e;
-            if (ctx->coarse_w4 && ctx->DP >= 64) {
-                switch (ctx->DP) {
-                case 64: e = launch_coarse_w4<64>(ctx, ca, blocks); break;
-                case 128: e = launch_coarse_w4<128>(ctx, ca, blocks); break;
-                default: e = launch_coarse_w4<256>(ctx, ca, blocks); break;
-                }
-            } else {
-                // MFMA shape: v_mfma_f32_16x16x32_f16 at D = 256 (+4 % by wall, A/B on one box: the chip holds a higher
-                // clock on it under this kernel's load), v_mfma_f32_32x32x16_f16 below (D = 128: -2.5 % on the other
-                // shape -- half the MFMA work per tile makes that kernel issue-bound, and 16x16x32 issues twice as many)
-                const int shape = ctx->coarse_shape >= 0 ? ctx->coarse_shape : (ctx->DP == 256 ? 1 : 0);
-                if (shape == 1) {
-                    switch (ctx->DP) {
-                    case 32: e = launch_coarse<32, 0, 1>(ctx, ca, blocks); break;
-                    case 64: e = launch_coarse<64, 0, 1>(ctx, ca, blocks); break;
-                    case 128: e = launch_coarse<128, 0, 1>(ctx, ca, blocks); break;
-                    default:
-#ifdef RCN_DIAG
-                        switch (ctx->ablate) {   // RCN_COARSE_ABL: timing experiments only (diagnostic build)
-                        case 1: e = launch_coarse<256, 1, 1>(ctx, ca, blocks); break;
-                        case 9: e = launch_coarse<256, 9, 1>(ctx, ca, blocks); break;
-                        default: e = launch_coarse<256, 0, 1>(ctx, ca, blocks); break;
-                        }
-#else
-                        e = launch_coarse<256, 0, 1>(ctx, ca, blocks);
-#endif
-                        break;
-                    }
-                } else {
-                    switch (ctx->DP) {
-                    case 32:
-#ifdef RCN_DIAG
-                        if (ctx->ablate == 1) { e = launch_coarse<32, 1, 0>(ctx, ca, blocks); break; }
-                        if (ctx->ablate == 2) { e = launch_coarse<32, 2, 0>(ctx, ca, blocks); break; }
-                        if (ctx->ablate == 6) { e = launch_coarse<32, 6, 0>(ctx, ca, blocks); break; }
-#endif
-                        e = launch_coarse<32>(ctx, ca, blocks); break;
-                    case 64: e = launch_coarse<64>(ctx, ca, blocks); break;
-                    case 128:
-#ifdef RCN_DIAG
-                        if (ctx->ablate == 1) { e = launch_coarse<128, 1, 0>(ctx, ca, blocks); break; }   // timing only: no top-2 fold
-                        if (ctx->ablate == 2) { e = launch_coarse<128, 2, 0>(ctx, ca, blocks); break; }   // timing only: values-only fold
-                        if (ctx->ablate == 6) { e = launch_coarse<128, 6, 0>(ctx, ca, blocks); break; }   // timing only: minimum-only fold (one operation per element)
-#endif
-                        e = launch_coarse<128>(ctx, ca, blocks); break;
-                    default: e = launch_coarse<256>(ctx, ca, blocks); break;
-                    }
-                }
-            }
-            RCN_HIP(e);
-            // the int8 form of K1 (D padded to 256, at most 4096 padded rows per image): fix_scale chose between the two on the device, the
-            // host launches both and the one whose flag does not match returns at once.
-            // MFMA shape: v_mfma_i32_16x16x64_i8 (A/B on one box, EXPERIMENTS.md section 4: 108.0 ms per 32 640-pair launch against 117.8 ms on
-            // v_mfma_i32_32x32x32_i8 and 198.8 ms on the fp16 kernel)
-            if (ctx->i8_allowed) {
-#ifdef RCN_DIAG
-                if (ctx->coarse_i8_shape == 0) e = launch_coarse_i8<0, 0>(ctx, ca, blocks);
-                else if (ctx->ablate == 1) e = launch_coarse_i8<1, 1>(ctx, ca, blocks);      // timing only: no top-2 fold
-                else
-#endif
-                e = launch_coarse_i8<0, 1>(ctx, ca, blocks);
-                RCN_HIP(e);
-            }
-        }
+        if (pl.mfma && (rc = launch_coarse_stage(ctx, pl, ck, ra, cand_c))) return rc;
         if (tm) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][1], st));
         ra.cand = cand_c;
         ra.pair_base = p0;
         ra.fb_list = ctx->fb_list.as<unsigned long long>(); ra.fb_count = ccnt;
         ra.sv_list = ctx->sv_list.as<unsigned long long>(); ra.sv_count = ccnt + 1;
         if (c > 0) RCN_HIP(hipMemsetAsync(ccnt, 0, 4 * sizeof(unsigned), st));
-        if (kq_max > 0) {
-            const int qblocks = (kq_max + 255) / 256;
-            dim3 g((unsigned)qblocks * (unsigned)np_c);
-            ra.qblocks = (kq_max + RCN_FB - 1) / RCN_FB;
-            k_filter<<<(unsigned)ra.qblocks * (unsigned)np_c, RCN_FT, 0, st>>>(ra);
+        if (pl.kq_max > 0) {
+            ra.qblocks = (pl.kq_max + RCN_FB - 1) / RCN_FB;
+            k_filter<<<(unsigned)ra.qblocks * (unsigned)ck.np, RCN_FT, 0, st>>>(ra);
             RCN_HIP(hipGetLastError());
             // sharded grid: the fp32 rows of the other ranks' images travel on a side stream while the
             // coarse pass runs on the fp16 payload; the exact stages are the first to read them
             if (ctx->f32_ready) RCN_HIP(hipStreamWaitEvent(st, ctx->f32_ready, 0));
-            if (mfma) {
-                if (vec4) k_rerank_lds<<<rerank_grid(ctx), 64, 0, st>>>(ra);
+            if (pl.mfma) {
+                if (pl.vec4) k_rerank_lds<<<rerank_grid(ctx), 64, 0, st>>>(ra);
                 else k_rerank_generic<<<ctx->prop.multiProcessorCount * 8, 256, 0, st>>>(ra);
                 RCN_HIP(hipGetLastError());
             }
             const int fb_blocks = ctx->prop.multiProcessorCount * 8;
-            const unsigned long long *brute = ra.fb_list;
-            const unsigned *brute_n = ccnt;
-            if (mid) {
+            if (pl.mid) {
                 // the middle tier takes the first RCN_MIDROWS rows of the list; what overflows its candidate lists lands in fb2
-                char *mw = ctx->mid_ws.as<char>();
-                MidArgs ma;
-                memset(&ma, 0, sizeof(ma));
-                ma.imgs = imgs; ma.pairs = pairs; ma.cand = cand_c; ma.fb_list = ra.fb_list; ma.fb_count = ccnt; ma.tacc_in = ra.fb_tacc;
-                if (defer) {
-                    // the chunk's rows join the call's list if they fit (then ccnt[0] is 0 and the kernels below find nothing to do)
-                    MidArgs md = ma;
-                    md.sc = ra.sc; md.kq_stride = kq_stride; md.D = ctx->D; md.all_to_fallback = ra.all_to_fallback; md.idx_mask = idx_mask;
-                    k_mid_defer<<<ctx->prop.multiProcessorCount * 2, 256, 0, st>>>(md, (unsigned long long *)(mw + mo_def), (float *)(mw + mo_defthr), (unsigned *)(mw + mo_deftacc), ccnt, (unsigned)mid_rows_cap);
-                    k_mid_defer_commit<<<1, 64, 0, st>>>(ccnt, (unsigned)mid_rows_cap);
-                }
-                ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc); ma.tacc = (unsigned *)(mw + mo_tacc);
-                ma.clist = (int32_t *)(mw + mo_cl); ma.fb2_list = (unsigned long long *)(mw + mo_fb2);
-                ma.hist = (unsigned *)(mw + mo_bins); ma.offs = ma.hist + (n_slots + 1); ma.cursor = ma.offs + (n_slots + 1); ma.ibase = ma.cursor + (n_slots + 1);
-                ma.n_items = ccnt + 3; ma.fb2_count = ccnt + 2;
-                ma.out = out_dev; ma.out_stride = out_stride; ma.sc = ra.sc; ma.n_slots = n_slots; ma.kq_stride = kq_stride; ma.D = ctx->D;
-                ma.all_to_fallback = ra.all_to_fallback; ma.idx_mask = idx_mask; ma.ratio = ratio; ma.midrows = (uint32_t)ctx->mid_rows;
-                const int mb = ctx->prop.multiProcessorCount * 4;
-                k_mid_hist<<<mb, 256, 0, st>>>(ma);
-                k_mid_bins<<<1, 1024, 0, st>>>(ma);
-                k_mid_scatter<<<mb, 256, 0, st>>>(ma);
-                k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
-                if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
-                launch_mid_exact(ctx, ma, st);
-                RCN_HIP(hipGetLastError());
-                // K2b: the overflow list, then the rows beyond the tier's budget (none unless a chunk leaves more than RCN_MIDROWS rows)
-                if (vec4) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ma.fb2_list, ma.fb2_count, ctx->D, ratio, out_dev, out_stride);
-                RCN_HIP(hipGetLastError());
-                if (cap_rows > ctx->mid_rows) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, brute, brute_n, ctx->D, ratio, out_dev, out_stride, (unsigned)ctx->mid_rows);
-            } else if (vec4) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, brute, brute_n, ctx->D, ratio, out_dev, out_stride);
-            else k_exact_rows<false><<<fb_blocks, 256, 0, st>>>(imgs, pairs, brute, brute_n, ctx->D, ratio, out_dev, out_stride);
+                if ((rc = launch_mid_tier(ctx, pl, ra, ccnt, {cand_c, ra.fb_list, ccnt, nullptr, ra.fb_tacc, (uint32_t)ctx->mid_rows}, pl.defer))) return rc;
+                // K2b for the rows beyond the tier's budget (none unless a chunk leaves more than RCN_MIDROWS rows)
+                if (pl.cap_rows > ctx->mid_rows) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ra.fb_list, ccnt, ctx->D, ratio, out_dev, out_stride, (unsigned)ctx->mid_rows);
+            } else if (pl.vec4) k_exact_rows_lds<<<fb_blocks, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ra.fb_list, ccnt, ctx->D, ratio, out_dev, out_stride);
+            else k_exact_rows<false><<<fb_blocks, 256, 0, st>>>(imgs, pairs, ra.fb_list, ccnt, ctx->D, ratio, out_dev, out_stride);
             RCN_HIP(hipGetLastError());
-            k_stats_acc<<<1, 64, 0, st>>>(ccnt, mid ? 1 : 0, (unsigned)ctx->mid_rows);
+            k_stats_acc<<<1, 64, 0, st>>>(ccnt, pl.mid ? 1 : 0, (unsigned)ctx->mid_rows);
+            RCN_HIP(hipGetLastError());
             if (tm) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][2], st));
-            if (!uniq_lds) k_unique_claim<<<g, 256, 0, st>>>(imgs, pairs, out_dev, out_stride, ctx->owner.as<int32_t>(), owner_stride, qblocks, p0);
-            RCN_HIP(hipGetLastError());
         }
-        if (defer) { /* uniqueness follows the deferred pass, for every pair at once */ }
-        else if (uniq_lds) k_unique_pair<<<np_c, 256, 0, st>>>(imgs, pairs, out_dev, out_stride, counts_dev, p0);
-        else {
-            const int eblocks = (int)((out_stride + 255) / 256);
-            dim3 g((unsigned)eblocks * (unsigned)np_c);
-            k_unique_emit<<<g, 256, 0, st>>>(imgs, pairs, out_dev, out_stride, ctx->owner.as<int32_t>(), owner_stride, counts_dev, eblocks, p0);
-        }
-        RCN_HIP(hipGetLastError());
-        if (tm) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][kq_max > 0 ? 3 : 2], st));
-        if (tm && kq_max <= 0) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][3], st));
+        if ((rc = launch_unique(ctx, pl, ra, counts_dev, p0, ck.np))) return rc;
+        if (tm) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][pl.kq_max > 0 ? 3 : 2], st));
+        if (tm && pl.kq_max <= 0) RCN_HIP(hipEventRecord(ctx->ev_c[evi][c][3], st));
     }
+
+    // ---- the deferred tail
     ctx->ev_tail_on[evi] = false;
-    if (defer) {
+    if (pl.defer) {
         // the deferred rows of every chunk in one pass of the tier (their thresholds came with them), K2b for what overflows its
         // candidate lists, then uniqueness for all pairs
         if (prof) { RCN_HIP(hipEventRecord(ctx->ev_tail[evi][0], st)); ctx->ev_tail_on[evi] = true; }
-        char *mw = ctx->mid_ws.as<char>();
+        const char *mw = ctx->mid_ws.as<char>();
         RCN_HIP(hipMemsetAsync(ccnt + 2, 0, 2 * sizeof(unsigned), st));      // fb2 count, work items
-        MidArgs ma;
-        memset(&ma, 0, sizeof(ma));
-        ma.imgs = imgs; ma.pairs = pairs; ma.cand = nullptr; ma.fb_list = (const unsigned long long *)(mw + mo_def); ma.fb_count = ccnt + 7;
-        ma.thr_in = (const float *)(mw + mo_defthr);
-        ma.tacc_in = mid_i8 ? (const unsigned *)(mw + mo_deftacc) : nullptr;
-        ma.sorted = (unsigned long long *)(mw + mo_sorted); ma.thr = (float *)(mw + mo_thr); ma.ccount = (unsigned *)(mw + mo_cc); ma.tacc = (unsigned *)(mw + mo_tacc);
-        ma.clist = (int32_t *)(mw + mo_cl); ma.fb2_list = (unsigned long long *)(mw + mo_fb2);
-        ma.hist = (unsigned *)(mw + mo_bins); ma.offs = ma.hist + (n_slots + 1); ma.cursor = ma.offs + (n_slots + 1); ma.ibase = ma.cursor + (n_slots + 1);
-        ma.n_items = ccnt + 3; ma.fb2_count = ccnt + 2;
-        ma.out = out_dev; ma.out_stride = out_stride; ma.sc = ra.sc; ma.n_slots = n_slots; ma.kq_stride = kq_stride; ma.D = ctx->D;
-        ma.all_to_fallback = ra.all_to_fallback; ma.idx_mask = idx_mask; ma.ratio = ratio; ma.midrows = (uint32_t)mid_rows_cap;
-        const int mb = ctx->prop.multiProcessorCount * 4;
-        k_mid_hist<<<mb, 256, 0, st>>>(ma);
-        k_mid_bins<<<1, 1024, 0, st>>>(ma);
-        k_mid_scatter<<<mb, 256, 0, st>>>(ma);
-        k_mid_eval<<<ctx->prop.multiProcessorCount * 4, 256, 0, st>>>(ma);
-        if (mid_i8) k_mid_eval_i8<<<mid_i8_grid, 256, 0, st>>>(ma);
-        launch_mid_exact(ctx, ma, st);
-        k_exact_rows_lds<<<ctx->prop.multiProcessorCount * 8, 64 * EX_WAVES, 0, st>>>(imgs, pairs, ma.fb2_list, ma.fb2_count, ctx->D, ratio, out_dev, out_stride);
+        if ((rc = launch_mid_tier(ctx, pl, ra, ccnt, {nullptr, (const unsigned long long *)(mw + mo.def), ccnt + 7, (const float *)(mw + mo.defthr),
+                                                      pl.mid_i8 ? (const unsigned *)(mw + mo.deftacc) : nullptr, (uint32_t)mo.rows_cap}, false))) return rc;
         k_stats_acc_deferred<<<1, 64, 0, st>>>(ccnt);
         RCN_HIP(hipGetLastError());
         if (prof) RCN_HIP(hipEventRecord(ctx->ev_tail[evi][1], st));
@@ -2853,14 +2775,15 @@ int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs,
         RCN_HIP(hipGetLastError());
         if (prof) RCN_HIP(hipEventRecord(ctx->ev_tail[evi][2], st));
     }
+
+    // ---- stats: the fallback count is read back lazily in rcn_match_last_stats
     if (prof) ctx->ev_n++;
     ctx->last_chunks = n_chunks;
-    ctx->last_kq_stride = kq_stride; ctx->last_idx_mask = idx_mask; ctx->last_n_pairs = n_pairs;
-    // stats: the fallback count is read back lazily in rcn_match_last_stats
-    ctx->last_stats.rows_total = rows;
-    ctx->last_stats.pair_distances = pd;
-    ctx->last_stats.used_mfma_path = mfma ? 1 : 0;
-    ctx->last_stats.coarse_dtype = mfma ? -1 : 0;      // which of the two: from the scale record, lazily (rcn_match_last_stats)
+    ctx->last_kq_stride = pl.kq_stride; ctx->last_idx_mask = pl.idx_mask; ctx->last_n_pairs = n_pairs;
+    ctx->last_stats.rows_total = pl.rows;
+    ctx->last_stats.pair_distances = pl.pair_distances;
+    ctx->last_stats.used_mfma_path = pl.mfma ? 1 : 0;
+    ctx->last_stats.coarse_dtype = pl.mfma ? -1 : 0;      // which of the two: from the scale record, lazily (rcn_match_last_stats)
     ctx->last_stats.rows_exact_fallback = -1;
     ctx->last_stats.err_bound_d2 = -1.0;      // from the scale constants, lazily (rcn_match_last_stats)
     return RCN_OK;
@@ -3173,20 +3096,21 @@ int rcn_diag_mid(rcn_ctx *ctx, int64_t *n_rows, unsigned long long *sorted_host,
 {
     if (!ctx || !n_rows) return RCN_ERR_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->diag_mid[0] || !ctx->mid_ws.p || ctx->last_chunks != 1) { ctx->set_error("rcn_diag_mid: the last grid call left no single pass of the middle tier"); return RCN_ERR_UNSUPPORTED; }
+    if (!ctx->grid.mid || !ctx->mid_ws.p || ctx->last_chunks != 1) { ctx->set_error("rcn_diag_mid: the last grid call left no single pass of the middle tier"); return RCN_ERR_UNSUPPORTED; }
     RCN_HIP(hipSetDevice(ctx->device));
+    const grid::MidLayout &mo = ctx->grid.mid_ws;
     unsigned c0 = 0;
     RCN_HIP(hipMemcpyAsync(&c0, ctx->counters.as<unsigned>() + 8, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     RCN_HIP(hipStreamSynchronize(ctx->stream));
-    const size_t n = std::min<size_t>(c0, ctx->diag_mid[5]);
+    const size_t n = std::min<size_t>(c0, mo.rows_cap);
     *n_rows = (int64_t)n;
     if (n == 0 || (!sorted_host && !tacc_host && !ccount_host && !clist_host)) return RCN_OK;
     if ((int64_t)n > cap) { ctx->set_error("rcn_diag_mid: the arrays are too short"); return RCN_ERR_ARG; }
     const char *mw = ctx->mid_ws.as<char>();
-    if (sorted_host) RCN_HIP(hipMemcpyAsync(sorted_host, mw + ctx->diag_mid[1], n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (tacc_host) RCN_HIP(hipMemcpyAsync(tacc_host, mw + ctx->diag_mid[2], n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ccount_host) RCN_HIP(hipMemcpyAsync(ccount_host, mw + ctx->diag_mid[3], n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (clist_host) RCN_HIP(hipMemcpyAsync(clist_host, mw + ctx->diag_mid[4], n * 4 * RCN_MIDCAP, hipMemcpyDeviceToHost, ctx->stream));
+    if (sorted_host) RCN_HIP(hipMemcpyAsync(sorted_host, mw + mo.sorted, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (tacc_host) RCN_HIP(hipMemcpyAsync(tacc_host, mw + mo.tacc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (ccount_host) RCN_HIP(hipMemcpyAsync(ccount_host, mw + mo.cc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (clist_host) RCN_HIP(hipMemcpyAsync(clist_host, mw + mo.cl, n * 4 * RCN_MIDCAP, hipMemcpyDeviceToHost, ctx->stream));
     RCN_HIP(hipStreamSynchronize(ctx->stream));
     return RCN_OK;
 }

@@ -17,9 +17,7 @@
 // The kernel returns at once unless fix_scale chose the int8 path for the resident set (ScaleDev::coarse_i8).
 #pragma once
 
-#define MI8_TR 512             // train rows per tile: two per thread
-#define MI8_QB 32              // query rows per LDS batch
-#define MI8_TILES ((1 << RCN_I8_IDX_BITS) / MI8_TR)   // tiles of the largest image the int8 path admits
+#define MI8_QB 32              // query rows per LDS batch (MI8_TR, the train rows per tile, and MI8_TILES: grid_plan.h -- the host plan sizes the grid by them)
 
 __global__ __launch_bounds__(256, 2) void k_mid_eval_i8(MidArgs a)
 {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rcn.h"
+#include "grid_plan.h"
 
 #define RCN_HIP(call)                                                                    \
     do {                                                                                 \
@@ -168,8 +169,8 @@ struct rcn_ctx {
     int32_t D = 0, DP = 0;
     std::map<int32_t, ImgHost> images;
     std::vector<Slab> slabs;
-    std::vector<int2> groups_host, groups_arranged;   // kept alive: uploaded asynchronously
-    std::vector<int32_t> slots_host;                  // pair list as table slots (same reason)
+    grid::GridShape grid_shape;                       // the last grid call's pair list as table slots and row counts, and its plan (grid_plan.h):
+    grid::GridPlan grid;                              // kept alive, their vectors are uploaded asynchronously
     std::vector<int32_t> all_pairs_host;              // the canonical i < j grid when the caller passes pairs == NULL
     bool prepared = false;
     double scale = 0.0;      // s, power of two (0 = nothing prepared yet)
@@ -237,7 +238,6 @@ struct rcn_ctx {
     bool mid_i8_off = false;   // RCN_MID_I8=0: on the int8 path too, every row of the middle tier takes the fp32 sweep (no k_mid_eval_i8)
     bool rerank_pass = false;  // RCN_RERANK_PASS=1: certify's verdict is ignored, every re-ranked row goes to the middle tier
     bool filter_pass = false;  // RCN_FILTER_PASS=1: k_filter certifies nothing, every row with a coarse pair goes to the re-rank
-    std::array<size_t, 6> diag_mid{};   // rcn_diag_mid: {the last grid call had a middle tier, offsets of sorted / tacc / ccount / clist in mid_ws, rows they hold}
     bool no_item_order = false;   // RCN_MATCH_NO_ORDER=1: work items in pair order instead of heaviest-first per XCD
     bool ba_atomics = false;   // RCN_BA_SCHUR_ATOMICS=1: atomic Schur accumulation instead of the gather form
     bool ba_trsv_fwd = false;  // RCN_BA_TRSV_FWD=1: separate forward substitution instead of the rhs row inside the factorisation
