@@ -7,7 +7,8 @@
 //   * v_mfma_i32_32x32x32_i8 (SH 0) / v_mfma_i32_16x16x64_i8 (SH 1): the accumulator is an EXACT integer,
 //         acc(q, t) = hn[t] - qq.tq,   hn[t] = rint(s^2 |t|^2 / 2) + BIAS   (k_prepare_i8),
 //     0 <= acc < 2^20 - 1 for every pair of resident rows (fix_scale caps s for that), padded rows have acc = 2^20 - 1;
-//   * the key is (acc << 12) | train row: ONE v_lshl_or_b32 with the shift as an inline constant, no truncation;
+//   * the key is (acc << 12) | train row: ONE v_lshl_or_b32 with the shift as an inline constant, no truncation; the keys
+//     are folded four at a time (top2_fold.h), one key behind every MFMA of the 16x16x64 shape;
 //   * query fragments are negated bytewise once per item (the grid is [-127, 127], so the negation cannot overflow).
 // The kernel returns at once unless fix_scale chose the int8 path for the resident set (ScaleDev::coarse_i8).
 #pragma once
@@ -140,6 +141,24 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
         m2[cb] = max(lo, min(hi, u));
         m1[cb] = min(m1[cb], u);
     };
+    // the shipping fold: four keys of a column block at a time, as in k_coarse_top2 (ABL 16 / 32 and LATE as there; on the 16x16 shape
+    // that ships the two placements measure the same)
+    constexpr bool LATE = ((ABL & 32) != 0) != (SH == 0);
+    unsigned fk[NCB][3], fs[NCB];
+    auto push = [&](int cb, int j, unsigned u) {
+        if constexpr ((ABL & 1) != 0) return;
+        if constexpr ((ABL & 16) != 0) { top2(cb, u); return; }
+        if constexpr (LATE) {
+            if ((j & 3) < 3) fk[cb][j & 3] = u;
+            else top2_fold4(m1[cb], m2[cb], fk[cb][0], fk[cb][1], fk[cb][2], u);
+            return;
+        }
+        switch (j & 3) {
+        case 0: case 2: fk[cb][0] = u; break;
+        case 1: fs[cb] = top2_fold_pair(m1[cb], fk[cb][0], u); break;
+        default: m2[cb] = umin3(m2[cb], fs[cb], top2_fold_pair(m1[cb], fk[cb][0], u)); break;
+        }
+    };
     // the key of an accumulator: the shift is an inline constant, the row an SGPR or a literal -> one v_lshl_or_b32
     auto key = [&](int acc, unsigned idx) -> unsigned { return ((unsigned)acc << RCN_I8_IDX_BITS) | idx; };
     // LDS reads of the ring go through inline asm (see k_coarse_top2): no s_waitcnt vmcnt(0) in front of them
@@ -176,11 +195,11 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
             c0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bq[0][ks], ks == 0 ? hnv : c0, 0, 0, 0);
 #pragma unroll
             for (int reg = ks * 16 / NKS; reg < (ks + 1) * 16 / NKS; ++reg)
-                top2(0, key(p0v[reg], prev_rowbase + (reg & 3) + 8 * (reg >> 2)));
+                push(0, reg, key(p0v[reg], prev_rowbase + (reg & 3) + 8 * (reg >> 2)));
             c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bq[1][ks], ks == 0 ? hnv : c1, 0, 0, 0);
 #pragma unroll
             for (int reg = ks * 16 / NKS; reg < (ks + 1) * 16 / NKS; ++reg)
-                top2(1, key(p1v[reg], prev_rowbase + (reg & 3) + 8 * (reg >> 2)));
+                push(1, reg, key(p1v[reg], prev_rowbase + (reg & 3) + 8 * (reg >> 2)));
         };
 #pragma unroll
         for (int ks = 0; ks < NKS; ks += 2) {
@@ -222,7 +241,7 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
 #pragma unroll
                     for (int e = ks * EPK + m * EPK / 8; e < ks * EPK + (m + 1) * EPK / 8; ++e) {
                         const int es = e >> 4, ecb = (e >> 2) & 3, er = e & 3;
-                        top2(ecb, key(pv[es][ecb][er], prev_rowbase + 16 * es + er));
+                        push(ecb, er, key(pv[es][ecb][er], prev_rowbase + 16 * es + er));
                     }
                 }
             };
@@ -283,14 +302,14 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const unsigned idx = rowbase + (reg & 3) + 8 * (reg >> 2);
-                    top2(0, key(pY0[reg], idx));
-                    top2(1, key(pY1[reg], idx));
+                    push(0, reg, key(pY0[reg], idx));
+                    push(1, reg, key(pY1[reg], idx));
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < 32; ++e) {
                     const int es = e >> 4, ecb = (e >> 2) & 3, er = e & 3;
-                    top2(ecb, key(qY[es][ecb][er], rowbase + 16 * es + er));
+                    push(ecb, er, key(qY[es][ecb][er], rowbase + 16 * es + er));
                 }
             }
         }

@@ -410,12 +410,7 @@ __global__ void k_fix_scale(const unsigned *__restrict__ counters, int DPa, int 
 }
 
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c)
-{
-    unsigned r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
+#include "top2_fold.h"
 
 // train rows per LDS tile of k_coarse_top2
 __host__ __device__ constexpr int coarse_bt(int DP) { return DP == 256 ? 64 : 128; }
@@ -440,14 +435,19 @@ struct CoarseArgs {
 //   lanes), C initialised with the train rows' biased half-norms, so each accumulator
 //   element is  s^2 * (|t|^2/2 - q.t) + BIAS  > 0  and orders like the squared distance for a
 //   fixed query.  Positive floats order like unsigned integers, so the running top-2 per
-//   (lane, column block) is v_and_or + v_med3_u32 + v_min_u32 per element, software-pipelined
+//   (lane, column block) is an integer fold of packed keys: v_and_or per element, then two
+//   v_med3_u32 and three v_min3_u32 per FOUR elements of a column block (top2_fold.h: 2.25
+//   vector operations per element, not the 3 of med3 + min per key), software-pipelined
 //   into the MFMA issue gaps of the next row block.
 //   Train tiles (64 rows + a private copy of their half-norms per wave) stream through an LDS
 //   ring of RCN_NBUF buffers by LDS-DMA, RCN_PD tiles ahead, across pair boundaries; one raw
 //   s_barrier per tile behind a counted s_waitcnt vmcnt (never 0 in steady state).
-// ABL (ablation bits, diagnostics only -- results are wrong unless ABL == 0):
-//   1 skip the top-2 epilogue, 2 fold the VALUES only (two vector operations per element instead of three: what an exact top-2
+// ABL (ablation bits, diagnostics only -- results are wrong with bits 1, 2, 4 or 8):
+//   1 skip the top-2 epilogue, 2 fold the VALUES only key by key (two vector operations per element: what an exact top-2
 //   without the index in the key would cost), 4 (with 2) keep the running MINIMUM only -- one operation per element, 8 stage only the first tiles.
+//   Correct results, for timing one fold against another in one library: 16 the fold key by key (pack, v_med3_u32, v_min_u32: three
+//   operations per element, the shipping fold before the batched one), 32 the batched fold in its OTHER placement (see LATE below: a quad's
+//   five operations behind the keys as they arrive where the shipping kernel has them behind the fourth key, and the reverse).
 // SH: MFMA shape.  0: v_mfma_f32_32x32x16_f16 (two 32-column blocks per wave, 16 accumulators per lane and tile);
 //   1: v_mfma_f32_16x16x32_f16 -- the same 64 query columns per wave as four 16-column blocks, a 32-row train block as
 //   two 16-row halves, 4 accumulators per lane and tile; same operand bytes per MAC from LDS, same registers, same
@@ -586,6 +586,30 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2(CoarseArgs a)
         m2[cb] = max(lo, min(hi, u));
         m1[cb] = min(m1[cb], u);
     };
+    // The shipping fold takes the keys of one column block FOUR at a time (top2_fold.h): key j of a quad (j is a compile-time
+    // count of the block's keys; a quad never leaves its row block) is parked, the second and the fourth close a pair with
+    // v_med3_u32 + v_min3_u32, the fourth adds one v_min3_u32 into m2 -- five operations per four keys behind their packing,
+    // the same (m1, m2) as top2() key by key, placed behind the MFMA whose gap the key arrives in.
+    // One kernel keeps the fold key by key: D = 256 on 16x16x32 sits at 256 VGPRs, and parking a key and a median there moved a
+    // spill reload into the tile loop, where it has to wait for the LDS-DMA queue to drain (EXPERIMENTS.md section 4).
+    constexpr bool SEQ = (ABL & (2 | 4 | 16)) != 0 || (DP == 256 && SH == 1);
+    // Where the five operations go is a choice by measurement (EXPERIMENTS.md section 4): behind the keys as they arrive (above), or all
+    // behind the quad's fourth key -- the 32x32 shape, whose gaps bring two or more keys at a time, is faster with the latter.
+    constexpr bool LATE = ((ABL & 32) != 0) != (SH == 0);
+    unsigned fk[NCB][3], fs[NCB];
+    auto push = [&](int cb, int j, unsigned u) {
+        if constexpr (SEQ) { top2(cb, u); return; }
+        if constexpr (LATE) {
+            if ((j & 3) < 3) fk[cb][j & 3] = u;
+            else top2_fold4(m1[cb], m2[cb], fk[cb][0], fk[cb][1], fk[cb][2], u);
+            return;
+        }
+        switch (j & 3) {
+        case 0: case 2: fk[cb][0] = u; break;
+        case 1: fs[cb] = top2_fold_pair(m1[cb], fk[cb][0], u); break;
+        default: m2[cb] = umin3(m2[cb], fs[cb], top2_fold_pair(m1[cb], fk[cb][0], u)); break;
+        }
+    };
     // LDS reads of the ring go through inline asm: hipcc would otherwise put s_waitcnt vmcnt(0)
     // in front of every ds_read that may alias an in-flight LDS-DMA.  Each consumer is preceded
     // by a wait statement that names the registers it is about to use ("+v"), so neither the
@@ -626,13 +650,13 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2(CoarseArgs a)
             if (!(ABL & 1)) {
 #pragma unroll
                 for (int reg = ks * 16 / KS; reg < (ks + 1) * 16 / KS; ++reg)
-                    top2(0, (ABL & 2) ? __float_as_uint(p0v[reg]) : ((__float_as_uint(p0v[reg]) & hmask) | (prev_rowbase + (reg & 3) + 8 * (reg >> 2))));
+                    push(0, reg, (ABL & 2) ? __float_as_uint(p0v[reg]) : ((__float_as_uint(p0v[reg]) & hmask) | (prev_rowbase + (reg & 3) + 8 * (reg >> 2))));
             }
             c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bq[1][ks], ks == 0 ? hnv : c1, 0, 0, 0);
             if (!(ABL & 1)) {
 #pragma unroll
                 for (int reg = ks * 16 / KS; reg < (ks + 1) * 16 / KS; ++reg)
-                    top2(1, (ABL & 2) ? __float_as_uint(p1v[reg]) : ((__float_as_uint(p1v[reg]) & hmask) | (prev_rowbase + (reg & 3) + 8 * (reg >> 2))));
+                    push(1, reg, (ABL & 2) ? __float_as_uint(p1v[reg]) : ((__float_as_uint(p1v[reg]) & hmask) | (prev_rowbase + (reg & 3) + 8 * (reg >> 2))));
             }
         };
 #pragma unroll
@@ -676,7 +700,7 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2(CoarseArgs a)
 #pragma unroll
                         for (int e = ks * EPK + m * EPK / 8; e < ks * EPK + (m + 1) * EPK / 8; ++e) {
                             const int es = e >> 4, ecb = (e >> 2) & 3, er = e & 3;
-                            top2(ecb, (__float_as_uint(pv[es][ecb][er]) & hmask) | (prev_rowbase + 16 * es + er));
+                            push(ecb, er, (__float_as_uint(pv[es][ecb][er]) & hmask) | (prev_rowbase + 16 * es + er));
                         }
                     }
                 }
@@ -737,14 +761,14 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2(CoarseArgs a)
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const unsigned idx = rowbase + (reg & 3) + 8 * (reg >> 2);
-                    top2(0, (__float_as_uint(pY0[reg]) & hmask) | idx);
-                    top2(1, (__float_as_uint(pY1[reg]) & hmask) | idx);
+                    push(0, reg, (__float_as_uint(pY0[reg]) & hmask) | idx);
+                    push(1, reg, (__float_as_uint(pY1[reg]) & hmask) | idx);
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < 32; ++e) {
                     const int es = e >> 4, ecb = (e >> 2) & 3, er = e & 3;
-                    top2(ecb, (__float_as_uint(qY[es][ecb][er]) & hmask) | (rowbase + 16 * es + er));
+                    push(ecb, er, (__float_as_uint(qY[es][ecb][er]) & hmask) | (rowbase + 16 * es + er));
                 }
             }
         }
@@ -2518,6 +2542,7 @@ static int launch_coarse_stage(rcn_ctx *ctx, const grid::GridPlan &pl, const gri
 #ifdef RCN_DIAG
                 switch (ctx->ablate) {   // RCN_COARSE_ABL: timing experiments only (diagnostic build)
                 case 1: e = launch_coarse<256, 1, 1>(ctx, ca, blocks); break;
+                case 16: e = launch_coarse<256, 16, 1>(ctx, ca, blocks); break;                      // the fold key by key (results correct)
                 case 9: e = launch_coarse<256, 9, 1>(ctx, ca, blocks); break;
                 default: e = launch_coarse<256, 0, 1>(ctx, ca, blocks); break;
                 }
@@ -2533,6 +2558,8 @@ static int launch_coarse_stage(rcn_ctx *ctx, const grid::GridPlan &pl, const gri
                 if (ctx->ablate == 1) { e = launch_coarse<32, 1, 0>(ctx, ca, blocks); break; }
                 if (ctx->ablate == 2) { e = launch_coarse<32, 2, 0>(ctx, ca, blocks); break; }
                 if (ctx->ablate == 6) { e = launch_coarse<32, 6, 0>(ctx, ca, blocks); break; }
+                if (ctx->ablate == 16) { e = launch_coarse<32, 16, 0>(ctx, ca, blocks); break; }
+                if (ctx->ablate == 32) { e = launch_coarse<32, 32, 0>(ctx, ca, blocks); break; }
 #endif
                 e = launch_coarse<32>(ctx, ca, blocks); break;
             case 64: e = launch_coarse<64>(ctx, ca, blocks); break;
@@ -2541,6 +2568,8 @@ static int launch_coarse_stage(rcn_ctx *ctx, const grid::GridPlan &pl, const gri
                 if (ctx->ablate == 1) { e = launch_coarse<128, 1, 0>(ctx, ca, blocks); break; }   // timing only: no top-2 fold
                 if (ctx->ablate == 2) { e = launch_coarse<128, 2, 0>(ctx, ca, blocks); break; }   // timing only: values-only fold
                 if (ctx->ablate == 6) { e = launch_coarse<128, 6, 0>(ctx, ca, blocks); break; }   // timing only: minimum-only fold (one operation per element)
+                if (ctx->ablate == 16) { e = launch_coarse<128, 16, 0>(ctx, ca, blocks); break; } // the fold key by key (results correct)
+                if (ctx->ablate == 32) { e = launch_coarse<128, 32, 0>(ctx, ca, blocks); break; } // the batched fold in its other placement (results correct)
 #endif
                 e = launch_coarse<128>(ctx, ca, blocks); break;
             default: e = launch_coarse<256>(ctx, ca, blocks); break;
@@ -2556,6 +2585,8 @@ static int launch_coarse_stage(rcn_ctx *ctx, const grid::GridPlan &pl, const gri
 #ifdef RCN_DIAG
         if (ctx->coarse_i8_shape == 0) e = launch_coarse_i8<0, 0>(ctx, ca, blocks);
         else if (ctx->ablate == 1) e = launch_coarse_i8<1, 1>(ctx, ca, blocks);      // timing only: no top-2 fold
+        else if (ctx->ablate == 16) e = launch_coarse_i8<16, 1>(ctx, ca, blocks);    // the fold key by key (results correct)
+        else if (ctx->ablate == 32) e = launch_coarse_i8<32, 1>(ctx, ca, blocks);    // the batched fold in its other placement (results correct)
         else
 #endif
         e = launch_coarse_i8<0, 1>(ctx, ca, blocks);

@@ -89,7 +89,7 @@ def main():
             for (kn2, c), (v, n) in sorted(tab.items()):
                 lines.append("%-44s %-28s n=%d mean=%.5g" % (kn2[:44], c, n, v))
     # the fold ablation at the SIFT shape (diagnostic build, RCN_COARSE_ABL): what a cheaper top-2 fold could buy at most
-    abl_names = {0: "shipping fold: and_or + med3 + min per element", 2: "values-only fold: med3 + min (results wrong by construction)", 6: "running minimum only: one operation (results wrong by construction)", 1: "no fold at all"}
+    abl_names = {0: "shipping fold: and_or per element + 2 med3 + 3 min3 per four", 16: "key-by-key fold: and_or + med3 + min per element", 2: "values-only fold: med3 + min (results wrong by construction)", 6: "running minimum only: one operation (results wrong by construction)", 1: "no fold at all"}
     if any(os.path.isdir(os.path.join(prof, "fold_abl%d" % a)) for a in abl_names):
         lines.append("")
         lines.append("## top-2 fold ablation, k_coarse_top2<128> at 100 x 1500 x 128 (tools/profile_round.sh, diagnostic build)")

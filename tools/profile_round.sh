@@ -28,8 +28,8 @@ run rocprofv3 --pmc FETCH_SIZE -d $O/k1_fetch_1000_4096_256 -o p --output-format
 run rocprofv3 --pmc WRITE_SIZE -d $O/k1_write_1000_4096_256 -o p --output-format csv -- python3 tools/k1_run.py 1000 4096 256 1 > $O/k1_write_cfg3.log 2>&1
 run rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $O/k1_sq_1000_4096_256 -o p --output-format csv -- python3 tools/k1_run.py 1000 4096 256 1 > $O/k1_sq_cfg3.log 2>&1
 run rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_VMEM -d $O/k1_lds_1000_4096_256 -o p --output-format csv -- python3 tools/k1_run.py 1000 4096 256 1 > $O/k1_lds_cfg3.log 2>&1
-# ---- the top-2 fold as a ceiling at the SIFT shape (diagnostic build): shipping fold (3 vector operations per accumulator element), values only (2), none
-for abl in 0 2 6 1; do
+# ---- the top-2 fold as a ceiling at the SIFT shape (diagnostic build): shipping fold (four keys at a time, 2.25 vector operations per accumulator element), key by key (16: 3 operations), values only (2), minimum only (6), none
+for abl in 0 16 2 6 1; do
   RCN_LIB=$PWD/tools/librcn_diag.so RCN_COARSE_ABL=$abl rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES -d $O/fold_abl$abl -o p --output-format csv -- python3 tools/k1_run.py 100 1500 128 6 > $O/fold_abl$abl.log 2>&1 || echo "   (rc=$?)"
 done
 fi
