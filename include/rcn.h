@@ -49,9 +49,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * 3 -> 4 added the triangulation entry points and rcn_triangulation_problem; 4 -> 5 the resident match lists, the 2D-3D
  * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
  * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options;
- * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*).
+ * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*; 10 -> 11 the robust losses rcn_ba_solve_robust, rcn_ba_session_set_loss,
+ * rcn_ba_session_loss_report).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 10
+#define RCN_ABI_REVISION 11
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -555,6 +556,34 @@ typedef struct {
 int rcn_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options,
                  rcn_ba_summary *summary);
 
+/* Robust losses.  The reference hands Ceres no loss (BundleAdjuster.cpp:89-93) and rcn_ba_solve means exactly that; the first
+ * thing a Ceres user switches on with real photographs is a HuberLoss or a CauchyLoss, and rcn_ba_solve_robust is that argument.
+ * The cost becomes 1/2 sum_o rho(s_o), s_o = r0^2 + r1^2 of observation o's residual in pixels^2, a = scale > 0 in pixels, b = a^2:
+ *   RCN_BA_LOSS_TRIVIAL  rho = s
+ *   RCN_BA_LOSS_HUBER    rho = s for s <= b, else 2 a sqrt(s) - b
+ *   RCN_BA_LOSS_SOFT_L1  rho = 2 b (sqrt(1 + s/b) - 1)
+ *   RCN_BA_LOSS_CAUCHY   rho = b log(1 + s/b)
+ * A restatement of Ceres' loss functions and Corrector from memory: PARITY WITH CERES IS UNPINNED.  All three have rho'' <= 0, so the
+ * corrector scales the residual and the Jacobian of an observation by sqrt(rho'(s)), rho' clamped from below at DBL_MIN, and nothing
+ * else; the line search (intrinsics_mode 1) takes the robust cost and sum_o rho'(s_o) r_o . (J_o d).
+ * With a loss, rcn_ba_summary's initial_cost, final_cost and cost_trace are ROBUST costs, and initial_rms_px / final_rms_px stay
+ * sqrt(2 cost / n_obs) of them: not a residual RMS any more -- rcn_ba_loss_report::plain_rms_px is.
+ * loss == NULL or RCN_BA_LOSS_TRIVIAL: rcn_ba_solve, bit for bit (the same kernels).  RCN_ERR_ARG with a message: an unknown kind, a
+ * scale that is not finite, a scale that is not positive under a non-trivial kind. */
+#define RCN_BA_LOSS_TRIVIAL 0
+#define RCN_BA_LOSS_HUBER   1
+#define RCN_BA_LOSS_SOFT_L1 2
+#define RCN_BA_LOSS_CAUCHY  3
+typedef struct { int32_t kind; int32_t reserved; double scale; } rcn_ba_loss;
+/* One pass over the observations at the solve's final point, on the unweighted residuals. */
+typedef struct {
+    int64_t n_obs, n_beyond_scale;              /* n_beyond_scale: observations with s > scale^2 (0 without a loss) */
+    double  plain_rms_px, max_residual_px;      /* sqrt(sum s / n_obs), sqrt(max s) */
+} rcn_ba_loss_report;
+/* loss, report and weights_host may each be NULL; weights_host: n_obs doubles, rho'(s_o) per observation (1 without a loss). */
+int rcn_ba_solve_robust(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options, const rcn_ba_loss *loss,
+                        rcn_ba_summary *summary, rcn_ba_loss_report *report, double *weights_host);
+
 /* Introspection, pure host code (no device, no ctx): the SCHEDULE of the dense factorisation inside rcn_ba_solve for a reduced system of
  * n_blocks 128-row blocks (csrc/chol_plan.h) -- the list of tile operations in an order that is a correct sequential algorithm, each
  * with its stream and the device counters it waits for, and the tile maps of the pipelined launches.  tests/test_chol_plan.py executes
@@ -598,6 +627,12 @@ int  rcn_ba_session_counts(const rcn_ba_session *s, int32_t *n_cams, int32_t *n_
 int  rcn_ba_session_graph(rcn_ba_session *s, int32_t *pt_out, int32_t *cam_out, int32_t *xy_out);
 /* options == NULL: rcn_ba_default_options for the current camera count (the reference's choice, BundleAdjuster.cpp:99-142) */
 int  rcn_ba_session_solve(rcn_ba_session *s, const rcn_ba_options *options, rcn_ba_summary *summary);
+/* The loss of every later rcn_ba_session_solve (kept across solves; NULL or RCN_BA_LOSS_TRIVIAL: none): rcn_ba_solve_robust's
+ * arithmetic on the same problem, bit for bit.  Argument errors as there. */
+int  rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss);
+/* rcn_ba_solve_robust's report and weights at the session's current state (its cameras, points and graph as they stand), under
+ * the session's loss; either pointer may be NULL, weights_host holds n_obs doubles. */
+int  rcn_ba_session_loss_report(rcn_ba_session *s, rcn_ba_loss_report *report, double *weights_host);
 int  rcn_ba_session_read_points(rcn_ba_session *s, double *xyz_host);
 const double *rcn_ba_session_points_device(rcn_ba_session *s);      /* n_points x 3 in HBM; valid until the next add / remove */
 /* checkLandmarkValidity (SequentialReconstructor.cpp:869-954) on the session's arrays, on the device.  poses34_host:

@@ -19,7 +19,7 @@ SYMBOLS = [
     "rcn_create", "rcn_destroy", "rcn_last_error", "rcn_version", "rcn_set_stream",
     "rcn_synchronize", "rcn_desc_upload", "rcn_desc_upload_device", "rcn_desc_upload_batch_device", "rcn_desc_upload_batch", "rcn_desc_remove", "rcn_desc_sample_device", "rcn_desc_sample_errors", "rcn_desc_sample_batch_device", "rcn_desc_clear",
     "rcn_desc_count", "rcn_match_pair", "rcn_match_grid", "rcn_match_grid_device",
-    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_factor_plan",
+    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_solve_robust", "rcn_ba_factor_plan",
     "rcn_landmark_validity", "rcn_landmark_validity_device",
     "rcn_fmat_filter", "rcn_fmat_filter_grid", "rcn_fmat_filter_grid_device",
     "rcn_coords_upload", "rcn_coords_upload_batch", "rcn_coords_clear", "rcn_match_table_filter_device",
@@ -30,7 +30,7 @@ SYMBOLS = [
     "rcn_shard_fail", "rcn_shard_set_timeout", "rcn_shard_gather_lists", "rcn_shard_merge_lists", "rcn_shard_profile", "rcn_shard_profile_read", "rcn_shard_filter", "rcn_match_grid_filtered",
     "rcn_ba_session_create", "rcn_ba_session_destroy", "rcn_ba_session_add_camera", "rcn_ba_session_cameras",
     "rcn_ba_session_add_points", "rcn_ba_session_add_observations", "rcn_ba_session_counts", "rcn_ba_session_graph",
-    "rcn_ba_session_solve", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
+    "rcn_ba_session_solve", "rcn_ba_session_set_loss", "rcn_ba_session_loss_report", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
     "rcn_ba_session_remove_outliers", "rcn_ba_session_triangulate",
     "rcn_triangulate", "rcn_triangulate_device",
     "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
@@ -169,6 +169,14 @@ class BaSummary(C.Structure):
                 ("cholesky_seconds", C.c_double), ("trisolve_seconds", C.c_double),
                 ("cost_trace", C.c_double * 160),
                 ("jacobian_seconds", C.c_double), ("jacobian_evals", C.c_int32), ("factor_schedule", C.c_int32)]
+
+
+class BaLoss(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double)]
+
+
+class BaLossReport(C.Structure):
+    _fields_ = [("n_obs", C.c_int64), ("n_beyond_scale", C.c_int64), ("plain_rms_px", C.c_double), ("max_residual_px", C.c_double)]
 
 
 _LIB = None
@@ -331,6 +339,8 @@ def load():
     L.rcn_ba_default_options.argtypes = [i32, C.POINTER(BaOptions)]
     L.rcn_ba_solve.restype = C.c_int
     L.rcn_ba_solve.argtypes = [vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]
+    L.rcn_ba_solve_robust.restype = C.c_int
+    L.rcn_ba_solve_robust.argtypes = [vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaLoss), C.POINTER(BaSummary), C.POINTER(BaLossReport), vp]
     for fn in (L.rcn_landmark_validity, L.rcn_landmark_validity_device):
         fn.restype = C.c_int
         fn.argtypes = [vp, C.POINTER(LandmarkProblem), C.c_double, C.c_double, vp, vp, vp]
@@ -417,6 +427,10 @@ def load():
     L.rcn_ba_session_graph.argtypes = [vp, vp, vp, vp]
     L.rcn_ba_session_solve.restype = C.c_int
     L.rcn_ba_session_solve.argtypes = [vp, C.POINTER(BaOptions), C.POINTER(BaSummary)]
+    L.rcn_ba_session_set_loss.restype = C.c_int
+    L.rcn_ba_session_set_loss.argtypes = [vp, C.POINTER(BaLoss)]
+    L.rcn_ba_session_loss_report.restype = C.c_int
+    L.rcn_ba_session_loss_report.argtypes = [vp, C.POINTER(BaLossReport), vp]
     L.rcn_ba_session_read_points.restype = C.c_int
     L.rcn_ba_session_read_points.argtypes = [vp, vp]
     L.rcn_ba_session_points_device.restype = vp

@@ -30,9 +30,27 @@ def summary_dict(s):
     return d
 
 
-def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=None, allow_failure=False):
+LOSS_KINDS = {"trivial": 0, "huber": 1, "soft_l1": 2, "cauchy": 3}
+
+
+def make_loss(loss):
+    """None, an rcn_ba_loss, or (kind, scale) with kind a name of LOSS_KINDS or its number -> _lib.BaLoss or None"""
+    if loss is None or isinstance(loss, _lib.BaLoss):
+        return loss
+    kind, scale = loss
+    return _lib.BaLoss(LOSS_KINDS[kind] if isinstance(kind, str) else int(kind), 0, float(scale))
+
+
+def loss_report_dict(r):
+    return {k: getattr(r, k) for k, _ in r._fields_}
+
+
+def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=None, allow_failure=False, loss=None, report=False):
     """Returns (poses, intrinsics, points, summary); inputs are copied, not modified.
-    allow_failure: a solve that ends in RCN_BA_FAILURE (RCN_ERR_NUMERIC; the summary is filled) returns instead of raising."""
+    allow_failure: a solve that ends in RCN_BA_FAILURE (RCN_ERR_NUMERIC; the summary is filled) returns instead of raising.
+    loss: None (rcn_ba_solve) or what make_loss takes (rcn_ba_solve_robust: Huber, soft-L1 or Cauchy with a scale in pixels; the
+    summary's costs are then robust costs).  report: the summary also carries "loss_report" (rcn_ba_loss_report as a dict) and
+    "loss_weights" (rho'(s) per observation) at the final point."""
     poses = np.array(poses, np.float64, order="C")
     intr = np.array(intrinsics, np.float64, order="C")
     pts = np.array(points, np.float64, order="C").reshape(-1, 3)
@@ -45,15 +63,25 @@ def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=
                         pt.ctypes.data if pt.size else None)
     o = options if options is not None else default_options(ctx, poses.shape[0])
     s = _lib.BaSummary()
-    rc = ctx.lib.rcn_ba_solve(ctx.h, C.byref(pb), C.byref(o), C.byref(s))
+    if loss is None and not report:
+        rc = ctx.lib.rcn_ba_solve(ctx.h, C.byref(pb), C.byref(o), C.byref(s))
+    else:
+        ls = make_loss(loss)
+        rep = _lib.BaLossReport()
+        w = np.zeros(max(cam.shape[0], 1))
+        rc = ctx.lib.rcn_ba_solve_robust(ctx.h, C.byref(pb), C.byref(o), C.byref(ls) if ls is not None else None, C.byref(s),
+                                         C.byref(rep) if report else None, w.ctypes.data if report else None)
     if not (allow_failure and rc == -6 and s.termination == 6):
         ctx.check(rc)
-    return poses, intr, pts, summary_dict(s)
+    d = summary_dict(s)
+    if report:
+        d["loss_report"], d["loss_weights"] = loss_report_dict(rep), w[:cam.shape[0]]
+    return poses, intr, pts, d
 
 
-def solve_scene(ctx, scene, options=None, allow_failure=False):
+def solve_scene(ctx, scene, options=None, allow_failure=False, loss=None, report=False):
     return solve_flat(ctx, scene["poses"], scene["intrinsics"], scene["points"], scene["obs_uv"],
-                      scene["obs_cam"], scene["obs_pt"], options, allow_failure)
+                      scene["obs_cam"], scene["obs_pt"], options, allow_failure, loss, report)
 
 
 def _rot_to_angle_axis(R):
@@ -78,9 +106,11 @@ def _angle_axis_to_rot(angle, axis):
 class BundleAdjuster:
     """Same call shape as the reference class (BundleAdjuster.h:76-85)."""
 
-    def __init__(self, ctx=None, device=0):
+    def __init__(self, ctx=None, device=0, loss=None):
+        """loss: None (the reference: no loss) or what make_loss takes, for every adjust()"""
         self.ctx = ctx if ctx is not None else _lib.Context(device)
         self.last_summary = None
+        self.loss = make_loss(loss)
 
     def adjust(self, features, landmarks, img_idx2cam_pose, img_idx2cam_intrinsics, img_idx_order):
         """features[img][feat] -> (x, y) integer pixel coords (or objects with .featCoord.x/.y);
@@ -105,7 +135,7 @@ class BundleAdjuster:
                 xy = (f.featCoord.x, f.featCoord.y) if hasattr(f, "featCoord") else (f[0], f[1])
                 uv.append((float(xy[0]), float(xy[1]))); cam.append(g2l[img]); pt.append(j)
         P, I, X, s = solve_flat(self.ctx, poses, intr, pts, np.array(uv).reshape(-1, 2),
-                                np.array(cam, np.int32), np.array(pt, np.int32))
+                                np.array(cam, np.int32), np.array(pt, np.int32), loss=self.loss)
         self.last_summary = s
         for j, lm in enumerate(landmarks):                              # :150-155
             if isinstance(lm, dict):
@@ -199,6 +229,18 @@ class BaSession:
         s = _lib.BaSummary()
         self.ctx.check(self.ctx.lib.rcn_ba_session_solve(self.h, C.byref(options) if options is not None else None, C.byref(s)))
         return summary_dict(s)
+
+    def set_loss(self, loss):
+        """the loss of every later solve (rcn_ba_session_set_loss): None switches it off"""
+        ls = make_loss(loss)
+        self.ctx.check(self.ctx.lib.rcn_ba_session_set_loss(self.h, C.byref(ls) if ls is not None else None))
+
+    def loss_report(self):
+        """(rcn_ba_loss_report as a dict, rho'(s) per observation) at the session's current state, under its loss"""
+        rep = _lib.BaLossReport()
+        w = np.zeros(max(self.counts()[2], 1))
+        self.ctx.check(self.ctx.lib.rcn_ba_session_loss_report(self.h, C.byref(rep), w.ctypes.data))
+        return loss_report_dict(rep), w[:self.counts()[2]]
 
     def validity(self, poses34=None, max_err=4.0, min_angle=1.0):
         """checkLandmarkValidity on the device arrays; returns (inlier flags, observations erased)."""

@@ -7,6 +7,8 @@
 //
 // Kernels:
 //   K4 k_ba_eval          residual (+ analytic 2x(10+3) tangent Jacobian) per observation   [HBM]
+//      (with a robust loss, rcn_ba_solve_robust: its ROBUST form scales the observation's row by sqrt(rho'), k_ba_dirgrad's takes
+//       rho' into the line search, k_ba_loss_report is the pass behind the solve; ba_loss.h)
 //   K5 k_ba_point_raw / k_ba_cam_raw   J'J blocks and J'r per point / per camera             [HBM]
 //      k_ba_point_solve   V = Vs + D^2/radius, V^-1, per point                               [HBM]
 //   K6 k_ba_wy + k_ba_schur_mfma[_wg] + k_ba_schur_diag_mfma   point Schur complement as f64-MFMA
@@ -21,6 +23,7 @@
 #include "wgprim.h"
 #include <utility>
 #include "ba_linesearch.h"
+#include "ba_loss.h"
 
 #include <cfloat>
 #include <chrono>
@@ -332,9 +335,14 @@ __device__ __forceinline__ void lds_to_rows(double *__restrict__ dst, size_t row
 
 // K4: residual and tangent Jacobian per observation; per-block partial of sum r^2.  JAC: every lane builds its row in
 // LDS, the wave stores its 64 rows as one contiguous block (HBM-bound: 224 B written per observation).
-template <bool JAC>
+// ROBUST (a loss, section 7.4; `ls` is read by that form alone): the per-observation term of the sum is rho(s), and the 28 entries of
+// the row are multiplied by sqrt(rho'(s)) AFTER they were built -- obs_residual and the column selection are the same expressions under
+// every loss, so a weight of exactly 1 leaves exactly the bits of the plain form.  The kind is uniform over the launch: a scalar branch.
+// Without a loss the solve launches ROBUST = false, which holds no loss code.
+struct BaLoss { int kind; double a, b; };
+template <bool JAC, bool ROBUST = false>
 __global__ __launch_bounds__(JAC ? 128 : 256) void k_ba_eval(BaDev d, const double *poses, const double *intr,
-                                                              const double *pts, double *partial, Fin fin)
+                                                              const double *pts, double *partial, Fin fin, BaLoss ls)
 {
     constexpr int NW = JAC ? 2 : 4;          // JAC: 30 KB of LDS per workgroup, five workgroups per CU
     __shared__ double sh[4];
@@ -350,6 +358,8 @@ __global__ __launch_bounds__(JAC ? 128 : 256) void k_ba_eval(BaDev d, const doub
         double r0, r1, J[2][15];
         obs_residual<JAC>(ps, in, X, d.uv + 2 * (size_t)o, r0, r1, J, JAC ? d.crot + CROT * (size_t)c : nullptr);
         c2 = r0 * r0 + r1 * r1;
+        double wt = 1.0;
+        if (ROBUST) { wt = ba_loss_weight(ls.kind, ls.a, ls.b, c2); c2 = ba_loss_rho(ls.kind, ls.a, ls.b, c2); }
         if (JAC) {
             // tangent columns of this camera, WITHOUT indexing J by a run-time column (that would put J in scratch
             // memory): the host lays them out as the first `npose` pose columns (0, 3 or 6: camera 0 / camera 1 / the
@@ -370,6 +380,10 @@ __global__ __launch_bounds__(JAC ? 128 : 256) void k_ba_eval(BaDev d, const doub
                 for (int k = 0; k < 3; ++k) row[20 + 3 * i + k] = J[i][12 + k];
             }
             row[26] = r0; row[27] = r1;
+            if (ROBUST) {
+#pragma unroll
+                for (int k = 0; k < JROW; ++k) row[k] *= wt;
+            }
             f64x2 *my = reinterpret_cast<f64x2 *>(stage + (w * 64 + lane) * JLD);
 #pragma unroll
             for (int k = 0; k < JCH; ++k) my[k] = (f64x2){row[2 * k], row[2 * k + 1]};
@@ -388,8 +402,10 @@ __global__ __launch_bounds__(JAC ? 128 : 256) void k_ba_eval(BaDev d, const doub
 // Line search (bounds present): directional derivative of the cost at a trial point along the step held in
 // d.dlc / d.dlp,  sum_o r_o' (Jc_o dlc + Jp_o dlp)  -- the tangent-space gradient J'r against the direction
 // (LineSearchFunction::Evaluate); nothing is stored, the Jacobian of an observation lives in registers.
+// With a loss (ROBUST) the observation's term is rho'(s) r_o' (J_o d): rho', not its square root -- the derivative of 1/2 rho(s).
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void k_ba_dirgrad(BaDev d, const double *poses, const double *intr,
-                                                     const double *pts, double *partial)
+                                                     const double *pts, double *partial, BaLoss ls)
 {
     __shared__ double sh[4];
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
@@ -408,9 +424,45 @@ __global__ __launch_bounds__(256) void k_ba_dirgrad(BaDev d, const double *poses
             for (int k = 0; k < 3; ++k) m += J[i][12 + k] * d.dlp[3 * (size_t)j + k];
             acc += r[i] * m;
         }
+        if (ROBUST) acc *= ba_loss_drho(ls.kind, ls.a, ls.b, r[0] * r[0] + r[1] * r[1]);
     }
     const double s = block_sum(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// The loss's report at one point (rcn_ba_loss_report): per observation rho'(s) into `weights` (optional), and over all observations
+// the count of s > b and sum s (finish_sums, index order) and max s (one integer atomicMax per workgroup, as k_ba_absmax: *maxout
+// zeroed by the caller).  s is the unweighted residual's, the expression of the evaluation kernels.
+__global__ __launch_bounds__(256) void k_ba_loss_report(BaDev d, const double *poses, const double *intr, const double *pts,
+                                                         BaLoss ls, double *weights, double *partial, Fin fin, double *maxout)
+{
+    __shared__ double sh[4];
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    double cnt = 0.0, ss = 0.0, m = 0.0;
+    if (o < d.no) {
+        const int c = d.ocam[o], j = d.opt[o];
+        double ps[6], in[6], X[3];
+        for (int i = 0; i < 6; ++i) { ps[i] = poses[6 * c + i]; in[i] = intr[6 * c + i]; }
+        for (int i = 0; i < 3; ++i) X[i] = pts[3 * j + i];
+        double r0, r1;
+        obs_residual<false>(ps, in, X, d.uv + 2 * (size_t)o, r0, r1, nullptr);
+        const double s = r0 * r0 + r1 * r1;
+        if (weights) weights[o] = ba_loss_drho(ls.kind, ls.a, ls.b, s);
+        cnt = s > ls.b ? 1.0 : 0.0;
+        ss = s;
+        m = s;
+    }
+    for (int k = 32; k; k >>= 1) { const double v = __shfl_down(m, k); if (v > m || v != v) m = v; }
+    __shared__ double shm[4];
+    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 4; ++i) if (shm[i] > m || shm[i] != shm[i]) m = shm[i];
+        atomicMax(reinterpret_cast<unsigned long long *>(maxout), (unsigned long long)__double_as_longlong(m));
+    }
+    const double c0 = block_sum(cnt, sh);
+    const double mine[2] = {c0, block_sum(ss, sh)};
+    finish_sums<2>(mine, partial, (int)gridDim.x, fin, sh);
 }
 
 // max |v| over two arrays (the line search's |direction|_inf); *out zeroed by the caller.  Non-negative doubles
@@ -1402,13 +1454,71 @@ int rcn_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *o
     return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr);
 }
 
+int rcn_ba_solve_robust(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, const rcn_ba_loss *loss, rcn_ba_summary *sum,
+                        rcn_ba_loss_report *report, double *weights_host)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr, loss, report, weights_host);
+}
+
 }  // extern "C"
+
+// The loss as the kernels take it.  NULL: no loss, and a report counts nothing beyond the scale (b = inf).
+int rcn_int_ba_loss_check(rcn_ctx *ctx, const rcn_ba_loss *loss, const char *who, int *kind, double *a, double *b)
+{
+    *kind = RCN_BA_LOSS_TRIVIAL; *a = *b = HUGE_VAL;
+    if (!loss) return RCN_OK;
+    if (loss->kind < RCN_BA_LOSS_TRIVIAL || loss->kind > RCN_BA_LOSS_CAUCHY) { ctx->set_error(std::string(who) + ": unknown loss kind"); return RCN_ERR_ARG; }
+    if (!std::isfinite(loss->scale)) { ctx->set_error(std::string(who) + ": the loss's scale is not finite"); return RCN_ERR_ARG; }
+    if (loss->kind != RCN_BA_LOSS_TRIVIAL && !(loss->scale > 0.0)) { ctx->set_error(std::string(who) + ": the loss's scale must be positive"); return RCN_ERR_ARG; }
+    if (loss->kind == RCN_BA_LOSS_TRIVIAL) return RCN_OK;      // (its scale means nothing)
+    *kind = loss->kind; *a = loss->scale; *b = loss->scale * loss->scale;
+    return RCN_OK;
+}
+
+// rcn_ba_loss_report at one point (ctx->mu held): everything in HBM except the results.  One launch of k_ba_loss_report; its scratch
+// (block partials, three scalars, the ticket, the weights) is ctx->ba_loss_ws, not the solver's workspace.
+int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const double *intr_dev, const double *pts_dev, const double *uv_dev,
+                           const int *ocam_dev, const int *opt_dev, const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host)
+{
+    BaLoss ls;
+    { const int rc = rcn_int_ba_loss_check(ctx, loss, "rcn_ba_loss_report", &ls.kind, &ls.a, &ls.b); if (rc) return rc; }
+    if (report) memset(report, 0, sizeof(*report));
+    if (no <= 0 || (!report && !weights_host)) return RCN_OK;
+    hipStream_t st = ctx->stream;
+    const int nb = (no + 255) / 256;
+    const size_t head = 2 * (size_t)nb + 8;      // partials [2][nb], then [0] count [1] sum s [2] max s, [4] the ticket word
+    RCN_HIP(ctx->ba_loss_ws.reserve((head + (weights_host ? (size_t)no : 0)) * sizeof(double)));
+    double *base = ctx->ba_loss_ws.as<double>(), *out = base + 2 * (size_t)nb, *w = weights_host ? base + head : nullptr;
+    RCN_HIP(hipMemsetAsync(out, 0, 8 * sizeof(double), st));
+    BaDev d;
+    memset(&d, 0, sizeof(d));
+    d.no = no; d.uv = uv_dev; d.ocam = ocam_dev; d.opt = opt_dev;
+    const Fin f{out, nullptr, reinterpret_cast<unsigned *>(out + 4), nullptr, nullptr, nullptr, 1.0, nullptr, nullptr, 0ull};
+    k_ba_loss_report<<<nb, 256, 0, st>>>(d, poses_dev, intr_dev, pts_dev, ls, w, base, f, out + 2);
+    RCN_HIP(hipGetLastError());
+    double h[3];
+    RCN_HIP(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, st));
+    if (w) RCN_HIP(hipMemcpyAsync(weights_host, w, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, st));
+    RCN_HIP(hipStreamSynchronize(st));
+    if (report) {
+        report->n_obs = no;
+        report->n_beyond_scale = (int64_t)h[0];
+        report->plain_rms_px = std::sqrt(h[1] / no);
+        report->max_residual_px = std::sqrt(h[2]);
+    }
+    return RCN_OK;
+}
 
 // The solve proper (ctx->mu held).  res == nullptr: everything comes from / goes back to the host arrays of the
 // problem.  res != nullptr (rcn_ba_session, ba_session.hip): the points and the observation arrays are already in HBM
 // and stay there -- pb->points may be NULL, pb->obs_* are the session's host mirror (structure only) -- and the pair
 // lists of the Schur build are reused when the token says the graph has not changed since they were built.
-int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res)
+// loss != nullptr with a non-trivial kind: the two kernels that evaluate observations run in their robust form (k_ba_eval<JAC, true>,
+// k_ba_dirgrad<true>); nothing else in the loop changes.  report / weights_host: one pass over the observations at the final point.
+int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
+                     const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host)
 {
     if (!pb || !opt || !sum || pb->n_cams <= 0 || pb->n_points < 0 || pb->n_obs < 0 || !pb->poses ||
         !pb->intrinsics || (pb->n_points > 0 && !pb->points && !res) ||
@@ -1416,6 +1526,9 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         ctx->set_error("rcn_ba_solve: bad argument");
         return RCN_ERR_ARG;
     }
+    BaLoss ls;
+    { const int rcl = rcn_int_ba_loss_check(ctx, loss, "rcn_ba_solve_robust", &ls.kind, &ls.a, &ls.b); if (rcl) return rcl; }
+    const bool robust = ls.kind != RCN_BA_LOSS_TRIVIAL;
     memset(sum, 0, sizeof(*sum));
     const int nc = pb->n_cams, np = pb->n_points, no = pb->n_obs;
     RCN_HIP(hipSetDevice(ctx->device));
@@ -1668,10 +1781,12 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
                 }
                 if (!rot_ready) k_ba_cam_rot<<<(nc + 127) / 128, 128, 0, st>>>(ps, nc, d.crot);      // (an accepted candidate brings its table: k_ba_plus)
                 if (phase_times) (void)hipEventRecord(ctx->ba_tev[4], st);
-                k_ba_eval<true><<<ebj, 128, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, false, d.scal + 12, nullptr, home));
+                if (robust) k_ba_eval<true, true><<<ebj, 128, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, false, d.scal + 12, nullptr, home), ls);
+                else k_ba_eval<true><<<ebj, 128, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, false, d.scal + 12, nullptr, home), ls);
                 if (phase_times) (void)hipEventRecord(ctx->ba_tev[5], st);
                 jac_pending = true;
-            } else k_ba_eval<false><<<eb, 256, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, with_flag, nullptr));
+            } else if (robust) k_ba_eval<false, true><<<eb, 256, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, with_flag, nullptr), ls);
+            else k_ba_eval<false><<<eb, 256, 0, st>>>(d, ps, in, x, d.partial, fin(d.scal + slot, 0.5, 0, with_flag, nullptr), ls);
         } else {
             k_finish_sum<<<1, 256, 0, st>>>(d.partial, 0, d.scal + slot, 0.5, with_flag ? d.flag : nullptr, d.scal + 13);      // no observations: the sums are zero
             if (jac) (void)hipMemsetAsync(d.scal + 12, 0, sizeof(double), st);
@@ -1903,7 +2018,8 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
                     break;
                 }
                 if (cur.v_ok) {
-                    if (no > 0) k_ba_dirgrad<<<eb, 256, 0, st>>>(d, d.poses2, d.intr2, d.pts2, d.partial);
+                    if (no > 0 && robust) k_ba_dirgrad<true><<<eb, 256, 0, st>>>(d, d.poses2, d.intr2, d.pts2, d.partial, ls);
+                    else if (no > 0) k_ba_dirgrad<false><<<eb, 256, 0, st>>>(d, d.poses2, d.intr2, d.pts2, d.partial, ls);
                     k_finish_sum<<<1, 256, 0, st>>>(d.partial, no > 0 ? eb : 0, d.scal + 10, 1.0);
                 }
                 if (dmax < 0.0) {                    // |delta|_inf, once per search (the first trial is a = 1)
@@ -1980,5 +2096,9 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         else RCN_HIP(hipMemcpyAsync(pb->points, d.pts, sizeof(double) * 3 * np, hipMemcpyDeviceToHost, st));
     }
     RCN_HIP(hipStreamSynchronize(st));
+    if (report || weights_host) {
+        const int rcr = rcn_int_ba_loss_report(ctx, no, d.poses, d.intr, d.pts, d.uv, d.ocam, d.opt, loss, report, weights_host);
+        if (rcr) return rcr;
+    }
     return termination == RCN_BA_FAILURE ? RCN_ERR_NUMERIC : RCN_OK;
 }

@@ -78,6 +78,8 @@ struct rcn_ba_session {
     bool obs_dirty = true;                           // device observation arrays do not reflect `tracks`
     std::vector<uint8_t> last_inlier;                // result of the last validity sweep (for remove_outliers)
     bool have_inlier = false;
+    rcn_ba_loss loss{RCN_BA_LOSS_TRIVIAL, 0, 0.0};   // rcn_ba_session_set_loss: the loss of every later solve (trivial: none)
+    DevBuf cams_dev;                                 // rcn_ba_session_loss_report: the cameras' 6 + 6 numbers, uploaded per call
 };
 
 #define SES_HIP(call)                                                                    \
@@ -148,7 +150,7 @@ void rcn_ba_session_destroy(rcn_ba_session *s)
         if ((ctx->ba_pair_token >> 32) == s->id) ctx->ba_pair_token = 0;
         s->pts.release();
         DevBuf *bufs[] = {&s->uv, &s->ocam, &s->opt, &s->xy, &s->pt_off, &s->poses34, &s->intr_dev, &s->inl, &s->keep, &s->cnt, &s->idx, &s->tmp_pts,
-                          &s->t_in, &s->t_xyz, &s->t_ws, &s->g_in};
+                          &s->t_in, &s->t_xyz, &s->t_ws, &s->g_in, &s->cams_dev};
         for (DevBuf *b : bufs) b->release();
     }
     delete s;
@@ -250,7 +252,42 @@ int rcn_ba_session_solve(rcn_ba_session *s, const rcn_ba_options *options, rcn_b
     BaResident res{static_cast<double *>(s->pts.p), s->uv.as<double>(), s->ocam.as<int>(), s->opt.as<int>(),
                    ((uint64_t)s->id << 32) | s->version};
     s->have_inlier = false;
-    return rcn_int_ba_solve(ctx, &pb, &o, summary, &res);    // poses / intrinsics come back into the host mirror, points stay in HBM
+    return rcn_int_ba_solve(ctx, &pb, &o, summary, &res,     // poses / intrinsics come back into the host mirror, points stay in HBM
+                            s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr);
+}
+
+int rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss)
+{
+    if (!s) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int kind;
+    double a, b;
+    const int rc = rcn_int_ba_loss_check(ctx, loss, "rcn_ba_session_set_loss", &kind, &a, &b);
+    if (rc) return rc;
+    s->loss = loss ? *loss : rcn_ba_loss{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
+    s->loss.reserved = 0;
+    return RCN_OK;
+}
+
+int rcn_ba_session_loss_report(rcn_ba_session *s, rcn_ba_loss_report *report, double *weights_host)
+{
+    if (!s) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t nc = s->poses.size() / 6;
+    SES_HIP(hipSetDevice(ctx->device));
+    int rc = sync_observations(s);
+    if (rc) return rc;
+    SES_HIP(s->cams_dev.reserve(std::max<size_t>(1, 12 * nc) * sizeof(double)));
+    double *cd = s->cams_dev.as<double>();
+    if (nc) {
+        SES_HIP(hipMemcpyAsync(cd, s->poses.data(), 6 * nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        SES_HIP(hipMemcpyAsync(cd + 6 * nc, s->intr.data(), 6 * nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // (a session whose loss is trivial reports like rcn_ba_solve_robust without one: nothing beyond the scale, weights 1)
+    return rcn_int_ba_loss_report(ctx, (int)s->n_obs, cd, cd + 6 * nc, static_cast<const double *>(s->pts.p), s->uv.as<double>(), s->ocam.as<int>(),
+                                  s->opt.as<int>(), s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr, report, weights_host);
 }
 
 int rcn_ba_session_read_points(rcn_ba_session *s, double *xyz_host)

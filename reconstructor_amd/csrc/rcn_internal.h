@@ -254,6 +254,7 @@ struct rcn_ctx {
 
     // ---- BA state (ba.hip)
     DevBuf ba_ws[40];
+    DevBuf ba_loss_ws;         // rcn_ba_loss_report's scratch: block partials, scalars, the per-observation weights
     DevBuf lm_ws;              // landmark validity sweep (validity.hip)
     DevBuf tri_ws, tri_dws;    // triangulation (triangulate.hip): host-API staging + workspace, workspace of the device entry
     DevBuf fm_ws, fm_state;    // epipolar filter (fmat.hip): host-API staging, per-pair RANSAC state
@@ -322,7 +323,12 @@ struct BaResident {
     const int *ocam, *opt;        // n_obs each, landmark-major
     uint64_t pair_token;          // identifies (session, graph version): pair lists built under the same token are reused
 };
-int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res);
+int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
+                     const rcn_ba_loss *loss = nullptr, rcn_ba_loss_report *report = nullptr, double *weights_host = nullptr);
+// ba.hip, ctx->mu held: the argument check of a loss (NULL: none); the loss's report at a point whose arrays are all in HBM
+int rcn_int_ba_loss_check(rcn_ctx *ctx, const rcn_ba_loss *loss, const char *who, int *kind, double *a, double *b);
+int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const double *intr_dev, const double *pts_dev, const double *uv_dev,
+                           const int *ocam_dev, const int *opt_dev, const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host);
 int rcn_match_release(rcn_ctx *ctx);
 // triangulate.hip, with ctx->mu held: the host-side structure check, the workspace size and the launches (all pointers in
 // HBM; compact / n_accepted may be NULL)

@@ -63,6 +63,12 @@ public:
     }
     ~BundleAdjuster() { if (owned_) rcn_destroy(ctx_); }
 
+    // A robust loss for every later adjust (what a Ceres user passes instead of the reference's nullptr, BundleAdjuster.cpp:89-93):
+    // RCN_BA_LOSS_HUBER / _SOFT_L1 / _CAUCHY with a scale in pixels; RCN_BA_LOSS_TRIVIAL switches it off.  `summary` then holds
+    // robust costs, and lossReport() the plain residual statistics of the last adjust (zeros while no loss is set).
+    void setLoss(int kind, double scale) { loss_ = rcn_ba_loss{(int32_t)kind, 0, scale}; }
+    const rcn_ba_loss_report &lossReport() const { return report_; }
+
     template <class Pose4>
     std::unordered_map<int, int> adjust(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
                                         std::vector<Landmark> &landmarks,
@@ -99,9 +105,11 @@ public:
                           pts.data(), uv.data(), cam.data(), pt.data()};
         rcn_ba_options opt;
         rcn_ba_default_options(nCams, &opt);                                // :99-142
-        const int rc = rcn_ba_solve(ctx_, &pb, &opt, &summary);
+        const bool robust = loss_.kind != RCN_BA_LOSS_TRIVIAL;
+        report_ = rcn_ba_loss_report{};
+        const int rc = rcn_ba_solve_robust(ctx_, &pb, &opt, robust ? &loss_ : nullptr, &summary, robust ? &report_ : nullptr, nullptr);   // no loss: rcn_ba_solve
         if (rc != RCN_OK && rc != RCN_ERR_NUMERIC)                          // the reference ignores Ceres' summary (:145-147)
-            throw std::runtime_error(std::string("rcn_ba_solve: ") + rcn_last_error(ctx_));
+            throw std::runtime_error(std::string("rcn_ba_solve_robust: ") + rcn_last_error(ctx_));
         for (size_t j = 0; j < landmarks.size(); ++j) {                     // :150-155
             landmarks[j].x = pts[3 * j]; landmarks[j].y = pts[3 * j + 1]; landmarks[j].z = pts[3 * j + 2];
         }
@@ -121,6 +129,8 @@ public:
 private:
     rcn_ctx *ctx_;
     bool owned_;
+    rcn_ba_loss loss_{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
+    rcn_ba_loss_report report_{};
 };
 
 }  // namespace reconstructor::Core

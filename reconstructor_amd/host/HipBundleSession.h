@@ -35,6 +35,20 @@ public:
     IncrementalBundleAdjuster(const IncrementalBundleAdjuster &) = delete;
     IncrementalBundleAdjuster &operator=(const IncrementalBundleAdjuster &) = delete;
 
+    // BundleAdjuster::setLoss / lossReport over the session: the loss is kept across adjusts and across rebuilds of the session; the
+    // report is evaluated at the session's current state (after an adjust: that adjust's result).
+    void setLoss(int kind, double scale)
+    {
+        loss_ = rcn_ba_loss{(int32_t)kind, 0, scale};
+        if (session_) check(rcn_ba_session_set_loss(session_, &loss_), "rcn_ba_session_set_loss");
+    }
+    rcn_ba_loss_report lossReport()
+    {
+        rcn_ba_loss_report r{};
+        if (session_) check(rcn_ba_session_loss_report(session_, &r, nullptr), "rcn_ba_session_loss_report");
+        return r;
+    }
+
     template <class Pose4>
     std::unordered_map<int, int> adjust(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
                                         std::vector<Landmark> &landmarks,
@@ -138,6 +152,7 @@ private:
         if (rcn_ba_session_create(ctx_, &session_) != RCN_OK)
             throw std::runtime_error(std::string("rcn_ba_session_create: ") + rcn_last_error(ctx_));
         order_.clear(); tracks_.clear(); xyz_.clear();
+        check(rcn_ba_session_set_loss(session_, &loss_), "rcn_ba_session_set_loss");
     }
     void check(int rc, const char *what) const
     {
@@ -151,6 +166,7 @@ private:
     std::vector<std::vector<std::pair<int, int>>> tracks_;      // (imgIdx, featIdx) per landmark, in track order
     std::vector<double> xyz_;                                   // landmark coordinates as written back by the last adjust
     int rebuilds_ = 0;
+    rcn_ba_loss loss_{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
 };
 
 }  // namespace reconstructor::Core

@@ -6,9 +6,11 @@
 //   ba_step_check DIR
 //
 // DIR/cases.txt, one case per line (lines that start with # are skipped):
-//   name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius [min_lm_diagonal max_lm_diagonal]
-// (the last two columns are optional and come together: absent, both stay as rcn_ba_default_options gives them, like every other
-//  option; max_iterations at least `iteration`).
+//   name scene iteration intrinsics_mode fix_cam0_pose fix_cam1_translation jacobi_scaling focal_upper_bound initial_radius [min_lm_diagonal max_lm_diagonal [loss_kind loss_scale]]
+// (the optional columns come in pairs: without the first pair both diagonals stay as rcn_ba_default_options gives them, like every other
+//  option; max_iterations at least `iteration`.  The second pair, which needs the first in front of it, is the robust loss of the solve,
+//  rcn_ba_loss's kind and scale: absent, there is none.  With it the case also writes DIR/<name>.weights, rho'(s) per observation at the
+//  point where the solve ended, and four "loss_*" lines of the report into the .meta).
 // DIR/<scene>.dims ("n_cams n_points n_obs" as text), .poses .intr .pts .uv (float64, little-endian) and .ocam .opt (int32): several
 // cases may name one scene -- the pair lists of the second are then the reused ones, as in the product.
 // Writes DIR/<name>.meta ("key value" lines: what the probe recorded as integers, the summary's iteration count and termination) and
@@ -45,7 +47,7 @@ template <class T> static bool write_raw(const std::string &path, const std::vec
     return fclose(f) == 0 && put == v.size();
 }
 
-struct StepCase { std::string name, scene; int iteration, mode, fix0, fix1, jacobi; double ub, radius, lm_lo, lm_hi; bool lm_given; };
+struct StepCase { std::string name, scene; int iteration, mode, fix0, fix1, jacobi; double ub, radius, lm_lo, lm_hi; bool lm_given; int loss_kind; double loss_scale; bool loss_given; };
 struct StepScene { std::string name; int nc = 0, np = 0, no = 0; std::vector<double> poses, intr, pts, uv; std::vector<int> ocam, opt; };
 
 static int run(const std::string &dir)
@@ -66,14 +68,23 @@ static int run(const std::string &dir)
             }
             // (optional trailing columns: both or neither, and nothing behind them)
             c.lm_given = false;
+            c.loss_given = false; c.loss_kind = 0; c.loss_scale = 0.0;
             std::string rest;
             if (ls >> rest) {
                 std::istringstream lo(rest);
-                if (!(lo >> c.lm_lo) || !lo.eof() || !(ls >> c.lm_hi) || (ls >> rest) || !(c.lm_lo >= 0.0) || !(c.lm_hi >= c.lm_lo)) {
+                if (!(lo >> c.lm_lo) || !lo.eof() || !(ls >> c.lm_hi) || !(c.lm_lo >= 0.0) || !(c.lm_hi >= c.lm_lo)) {
                     fprintf(stderr, "cases.txt: cannot parse \"%s\"\n", line.c_str());
                     return 2;
                 }
                 c.lm_given = true;
+                if (ls >> rest) {
+                    std::istringstream lk(rest);
+                    if (!(lk >> c.loss_kind) || !lk.eof() || !(ls >> c.loss_scale) || (ls >> rest)) {
+                        fprintf(stderr, "cases.txt: cannot parse \"%s\"\n", line.c_str());
+                        return 2;
+                    }
+                    c.loss_given = true;
+                }
             }
             cases.push_back(c);
         }
@@ -125,7 +136,11 @@ static int run(const std::string &dir)
         probe.iteration = c.iteration;
         ctx->ba_probe = &probe;
         rcn_ba_summary sum;
-        const int rc = rcn_int_ba_solve(ctx, &pb, &o, &sum, nullptr);
+        const rcn_ba_loss loss{c.loss_kind, 0, c.loss_scale};
+        rcn_ba_loss_report rep;
+        std::vector<double> weights(c.loss_given ? (size_t)sc.no : 0);
+        const int rc = c.loss_given ? rcn_int_ba_solve(ctx, &pb, &o, &sum, nullptr, &loss, &rep, weights.data())
+                                    : rcn_int_ba_solve(ctx, &pb, &o, &sum, nullptr);
         ctx->ba_probe = nullptr;
         if (rc != RCN_OK) { fprintf(stderr, "case %s: rcn_int_ba_solve returned %d: %s\n", c.name.c_str(), rc, ctx->err.c_str()); return 1; }
         CKT(hipGetLastError());
@@ -140,9 +155,12 @@ static int run(const std::string &dir)
                         q.got_a, q.got_b, q.n, q.npad, q.csplit, q.offdiag_kernel, q.diag_smb, q.fin, q.rhs_row, q.fused_finish, q.chain, q.pair_path);
                 fprintf(f, "iterations %d\ntermination %d\npair_lists_reused %d\nbound_projections %d\nradius %.17g\n", sum.iterations, sum.termination, sum.pair_lists_reused,
                         sum.bound_projections, q.radius);
+                if (c.loss_given) fprintf(f, "loss_n_obs %lld\nloss_n_beyond_scale %lld\nloss_plain_rms_px %.17g\nloss_max_residual_px %.17g\n", (long long)rep.n_obs,
+                                          (long long)rep.n_beyond_scale, rep.plain_rms_px, rep.max_residual_px);
                 ok = fclose(f) == 0;
             }
         }
+        if (c.loss_given) ok = ok && write_raw(b + ".weights", weights);
         const BaProbe &q = probe;
 #define PUT(field) ok = ok && write_raw(b + "." #field, q.field)
         PUT(J); PUT(crot); PUT(Uraw); PUT(gcraw); PUT(Vraw); PUT(gpraw); PUT(sc); PUT(sp); PUT(dgc); PUT(dgp); PUT(Vinv); PUT(gps); PUT(WY); PUT(S); PUT(rhs);
@@ -158,6 +176,7 @@ static int run(const std::string &dir)
     g_case = "-";
     CKT(hipStreamSynchronize(ctx->stream));
     for (DevBuf &w : ctx->ba_ws) w.release();
+    ctx->ba_loss_ws.release();
     (void)hipEventDestroy(ctx->ba_pair_ev);
     for (auto &e : ctx->ba_tev) (void)hipEventDestroy(e);
     rcn_chol_destroy(ctx);
