@@ -41,10 +41,24 @@ def data_sets():
     return out
 
 
-def measure(m, lib, q, t):
+def kernel_form(DP):
+    """The MFMA instruction of the fp16 coarse kernel that the diagnostic build's switches select for a padded length DP."""
+    if os.environ.get("RCN_COARSE_W4") == "1" and DP >= 64:
+        return "k_coarse_w4 (one wave per tile), v_mfma_f32_32x32x16_f16"
+    s16 = os.environ.get("RCN_COARSE_S16")
+    shape = (1 if s16[:1] == "1" else 0) if s16 else (1 if DP == 256 else 0)
+    return "k_coarse_top2, " + ("v_mfma_f32_16x16x32_f16" if shape else "v_mfma_f32_32x32x16_f16")
+
+
+def measure(m, lib, q, t, detail=False, batch=False):
+    """detail: also return, per query, the signed excursion of the worse candidate in eps (+: the accumulator lies above the exact
+    value, -: below), the train row that caused it, the packed table and eps.  batch: ingest through upload_batch (k_prepare_batch)."""
     m.clear()
-    m.upload(0, q)
-    m.upload(1, t)
+    if batch:
+        m.upload_batch(0, [q, t])
+    else:
+        m.upload(0, q)
+        m.upload(1, t)
     m.match_grid(np.array([[0, 1]], np.int32), len(q))
     model = (C.c_double * 8)()
     m.ctx.check(lib.rcn_diag_coarse_table(m.ctx.h, None, 0, model))
@@ -67,11 +81,15 @@ def measure(m, lib, q, t):
     idx = (cand & np.uint32(mask)).astype(np.int64)
     rows = np.arange(K1)
     worst = 0.0
+    signed, cause = np.zeros(K1), np.full(K1, -1, np.int64)
     for c in range(2):
         a = A[rows, idx[:, c]]
         out = np.maximum(np.maximum(lo[:, c] - a, a - hi[:, c]), 0.0) / eps
         assert (out <= 1.0).all(), ("candidate outside the bound", c, float(out.max()))
         worst = max(worst, float(out.max()))
+        more = out > np.abs(signed)
+        signed[more] = np.where(lo[:, c] - a > 0.0, out, -out)[more]
+        cause[more] = idx[more, c]
     nc = A.copy()
     nc[rows, idx[:, 0]] = np.inf
     nc[rows, idx[:, 1]] = np.inf
@@ -80,9 +98,13 @@ def measure(m, lib, q, t):
     worst_nc = float(short.max())
     # the exact top-2 of every row is among what the bound allows: sanity of the proposal itself
     quantum = float((hi - lo).max())
-    return {"K1": K1, "K2": K2, "DP": int(DP), "scale_log2": float(np.log2(s)), "eps_max": float(eps.max()), "eps_min": float(eps.min()),
-            "quantum_max": quantum, "candidate_excess_over_quantisation_interval_in_eps": worst,
-            "non_candidate_shortfall_in_eps": worst_nc, "rows": int(K1), "pair_distances_checked": int(K1) * int(K2)}
+    res = {"K1": K1, "K2": K2, "DP": int(DP), "scale_log2": float(np.log2(s)), "eps_max": float(eps.max()), "eps_min": float(eps.min()),
+           "quantum_max": quantum, "candidate_excess_over_quantisation_interval_in_eps": worst,
+           "non_candidate_shortfall_in_eps": worst_nc, "rows": int(K1), "pair_distances_checked": int(K1) * int(K2)}
+    if not detail:
+        return res
+    return res, {"signed_excursion_in_eps": signed, "row": cause, "cand": cand, "idx": idx, "eps": eps, "exact": A, "lo": lo, "hi": hi,
+                 "model": {"s": s, "bias": bias, "nmax": nmax, "DP": int(DP), "hn_max": hn_max}}
 
 
 def main():
@@ -99,7 +121,7 @@ def main():
         res[name] = measure(m, lib, np.ascontiguousarray(q), np.ascontiguousarray(t))
         print(name, json.dumps(res[name]), flush=True)
     res["_note"] = ("units of eps(q): 0 = the exact accumulator lies inside the truncated candidate's quantisation interval, "
-                    "1 = at the certified bound; measured on MI355X with v_mfma_f32_32x32x16_f16")
+                    "1 = at the certified bound; measured on MI355X, DP = 256: %s; DP < 256: %s" % (kernel_form(256), kernel_form(128)))
     if len(sys.argv) > 1:
         json.dump(res, open(sys.argv[1], "w"), indent=1)
 
