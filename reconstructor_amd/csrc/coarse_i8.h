@@ -10,12 +10,40 @@
 //   * the key is (acc << 12) | train row: ONE v_lshl_or_b32 with the shift as an inline constant, no truncation; the keys
 //     are folded four at a time (top2_fold.h), one key behind every MFMA of the 16x16x64 shape;
 //   * query fragments are negated bytewise once per item (the grid is [-127, 127], so the negation cannot overflow).
+//   * ONE half-norm image per ring buffer (512 bytes behind the tile), not one per wave: of the eight waves the one with
+//     w == (tile number & 7) brings it with a single 16-byte-wide LDS-DMA on lanes 0..31, after its four tile pieces.  The issuer rotates
+//     with the tile, so no wave is the straggler at every barrier.
+//     The counted waits are vmcnt(2 NINST) / vmcnt(NINST), the same immediates for every wave, and they are never too small: a wave has
+//     issued, behind the pieces of the tile it is about to read, NINST operations per later tile plus at most ONE half-norm piece (two
+//     consecutive tiles have different issuers).  If that piece belongs to a later tile, the wave waits for one operation more than it
+//     needs -- the oldest piece of the next tile, issued a whole tile of MFMAs ago; if it belongs to the tile about to be read, it is
+//     older than the 2 NINST (NINST) youngest and the wait covers it.  The barrier behind the wait then orders every other wave's pieces,
+//     the issuer's half-norm piece among them.  (hn holds Kp >= nT BT integers per image: the piece never reads past the image.)
+//   * on the 16x16x64 shape every LDS read is  ds_read_b128 v, base offset:imm  (coarse_i8_addr.h): four fragment bases and one half-norm
+//     base per lane, added to the ring buffer's address once per tile, row block and 16-row half in the immediate; and the four
+//     reads that open row block rb + 1 of a tile (two half-norm quads, the first fragment of each half) are issued in the last k-step
+//     of row block rb into registers of their own, so that only the first row block of a tile waits for LDS with nothing to do.
+//     The reads are asm with an early-clobber result ("=&v", EXPERIMENTS.md section 4): the result lands when the data returns and must
+//     never share a register with an address that a later read still uses.
 // The kernel returns at once unless fix_scale chose the int8 path for the resident set (ScaleDev::coarse_i8).
 #pragma once
+
+#include "coarse_i8_addr.h"
 
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+
+template <int V> struct I8Const { static constexpr int value = V; };
+
+// ds_read_b128 with the row block's part of the address as the instruction's immediate; no s_waitcnt vmcnt(0) in front (asm)
+template <unsigned IMM> __device__ __forceinline__ u32x4 lds_read_imm(unsigned base)
+{
+    static_assert(IMM < i8addr::OFFSET_LIMIT && IMM % 16 == 0, "offset field");
+    u32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(base), "n"(IMM));
+    return v;
+}
 
 // bytewise two's-complement negation of four int8 (no byte is -128)
 __device__ __forceinline__ unsigned neg_i8x4(unsigned w)
@@ -36,9 +64,8 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
     constexpr int TILEB = BT * ROWB;
     constexpr int PIECE = 64 * 16;
     constexpr int NINST = TILEB / 8 / PIECE;         // tile pieces per wave
-    constexpr int HNP = BT / 64;                     // half-norm pieces (64 rows each) per wave
-    constexpr int NG = NINST + HNP;
-    constexpr int BUFB = TILEB + 8 * BT * 4;
+    constexpr int BUFB = i8addr::BUF_BYTES;          // tile + one half-norm image
+    static_assert(ROWB == i8addr::ROW_BYTES && BT == i8addr::TILE_ROWS && BT * 4 == 32 * 16, "coarse_i8_addr.h describes another tile");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     if (!a.sc->coarse_i8) return;
@@ -119,11 +146,10 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
                 (const __attribute__((address_space(1))) void *)src,
                 (__attribute__((address_space(3))) void *)(bbase + off), 16, 0, 0);
         }
-#pragma unroll
-        for (int hp = 0; hp < HNP; ++hp)
+        if (w == (staged & 7) && lane < 32)         // the tile's 128 half-norms, once for the workgroup
             __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(s_hn + s_tile * BT + 64 * hp + lane),
-                (__attribute__((address_space(3))) void *)(bbase + TILEB + w * (BT * 4) + 256 * hp), 4, 0, 0);
+                (const __attribute__((address_space(1))) void *)(s_hn + s_tile * BT + 4 * lane),
+                (__attribute__((address_space(3))) void *)(bbase + TILEB), 16, 0, 0);
         ++staged;
         if (++s_tile == s_nT) { ++s_pair; s_seek(); }
     };
@@ -211,27 +237,50 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
     // SH 1.  cur <- hn + A.B for row block (tile, rb) as 2 halves x 4 column blocks of 16x16x64 MFMAs; the 32 values a
     // lane holds of the row block before it are folded into the top-2 between them.  Element (half s, block cb, reg)
     // is train row 16 s + 4 h + reg of the block: 16 s + reg goes into the packed index here, 4 h at the very end.
-    auto step16 = [&](i32x4 (&c)[2][4], const i32x4 (&pv)[2][4], unsigned tile, unsigned hnl, int rb, unsigned prev_rowbase) {
+    // Addresses (coarse_i8_addr.h): fl[ks] / hl are the lane's constants, set once per item; fb[ks] / hb add the ring buffer's address once
+    // per tile; the row block and the half are the read's immediate, so rb and ks are compile-time here (I8Const).
+    // open[] holds the block's opening reads {hA, hB, f0a, f0b}: issued here behind the barrier for the first block of a tile, by the
+    // last k-step of the block before for the others, which in turn issues the next block's into next[].
+    unsigned fl[4], hl = 0, fb[4], hb = 0;
+    if constexpr (SH == 1) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) fl[ks] = i8addr::frag_lane((unsigned)r, (unsigned)h, (unsigned)ks);
+        hl = i8addr::hn_lane((unsigned)h);
+        asm volatile("" : "+v"(fl[0]), "+v"(fl[1]), "+v"(fl[2]), "+v"(fl[3]), "+v"(hl));   // five resident registers, not recomputed per read
+    }
+    constexpr bool EARLY = RCN_I8_EARLY_OPEN != 0;
+    auto step16 = [&](auto RB, i32x4 (&c)[2][4], i32x4 (&pv)[2][4], u32x4 (&open)[4], u32x4 (&next)[4], unsigned prev_rowbase) {
         if constexpr (SH == 1) {
-            const int lrow = rb * 32 + r;                    // + 16 for the second half: same swizzle (period 16 rows)
-            const unsigned arow0 = tile + lrow * ROWB, arow1 = arow0 + 16 * ROWB;
-            const int sw = lrow & 15;
-            u32x4 hA, hB, f0a, f0b, f1a, f1b;
-            hA = lds_read(hnl + (rb * 32 + 0 + 4 * h) * 4);
-            hB = lds_read(hnl + (rb * 32 + 16 + 4 * h) * 4);
-            f0a = lds_read(arow0 + ((h ^ sw) << 4));
-            f0b = lds_read(arow1 + ((h ^ sw) << 4));
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(hA), "+v"(hB), "+v"(f0a), "+v"(f0b));
+            constexpr int rb = decltype(RB)::value;
+            constexpr bool opened = EARLY && rb > 0;         // the block before issued open[]
+            if constexpr (!opened) {
+                open[0] = lds_read_imm<i8addr::hn_imm(rb, 0)>(hb);
+                open[1] = lds_read_imm<i8addr::hn_imm(rb, 1)>(hb);
+                open[2] = lds_read_imm<i8addr::frag_imm(rb, 0)>(fb[0]);
+                open[3] = lds_read_imm<i8addr::frag_imm(rb, 1)>(fb[0]);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(open[0]), "+v"(open[1]), "+v"(open[2]), "+v"(open[3]));
+            } else {
+                // naming the block before's last accumulator ties the wait BEHIND its MFMAs
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(open[0]), "+v"(open[1]), "+v"(open[2]), "+v"(open[3]), "+v"(pv[1][3]));
+            }
             i32x4 hn[2];
-            hn[0] = __builtin_bit_cast(i32x4, hA);
-            hn[1] = __builtin_bit_cast(i32x4, hB);
+            hn[0] = __builtin_bit_cast(i32x4, open[0]);
+            hn[1] = __builtin_bit_cast(i32x4, open[1]);
+            u32x4 &f0a = open[2], &f0b = open[3];
+            u32x4 f1a, f1b;
             constexpr int EPK = 32 / NKS;                    // previous-block elements folded per k-step
-            auto kstep = [&](int ks, u32x4 &ca_, u32x4 &cb_, u32x4 &na_, u32x4 &nb_) {
+            auto kstep = [&](auto KS, u32x4 &ca_, u32x4 &cb_, u32x4 &na_, u32x4 &nb_) {
+                constexpr int ks = decltype(KS)::value;
                 // naming the last accumulator ties the wait BEHIND the previous k-step's MFMAs
-                if (ks > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ca_), "+v"(cb_), "+v"(c[1][3]));
-                if (ks + 1 < NKS) {
-                    na_ = lds_read(arow0 + ((((ks + 1) * 4 + h) ^ sw) << 4));
-                    nb_ = lds_read(arow1 + ((((ks + 1) * 4 + h) ^ sw) << 4));
+                if constexpr (ks > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ca_), "+v"(cb_), "+v"(c[1][3]));
+                if constexpr (ks + 1 < NKS) {
+                    na_ = lds_read_imm<i8addr::frag_imm(rb, 0)>(fb[(ks + 1) & 3]);
+                    nb_ = lds_read_imm<i8addr::frag_imm(rb, 1)>(fb[(ks + 1) & 3]);
+                } else if constexpr (EARLY && rb + 1 < BT / 32) {
+                    next[0] = lds_read_imm<i8addr::hn_imm(rb + 1, 0)>(hb);
+                    next[1] = lds_read_imm<i8addr::hn_imm(rb + 1, 1)>(hb);
+                    next[2] = lds_read_imm<i8addr::frag_imm(rb + 1, 0)>(fb[0]);
+                    next[3] = lds_read_imm<i8addr::frag_imm(rb + 1, 1)>(fb[0]);
                 }
                 const i32x4 av[2] = {__builtin_bit_cast(i32x4, ca_), __builtin_bit_cast(i32x4, cb_)};
 #pragma unroll
@@ -245,11 +294,10 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
                     }
                 }
             };
-#pragma unroll
-            for (int ks = 0; ks < NKS; ks += 2) {
-                kstep(ks, f0a, f0b, f1a, f1b);
-                kstep(ks + 1, f1a, f1b, f0a, f0b);
-            }
+            kstep(I8Const<0>{}, f0a, f0b, f1a, f1b);
+            kstep(I8Const<1>{}, f1a, f1b, f0a, f0b);
+            kstep(I8Const<2>{}, f0a, f0b, f1a, f1b);
+            kstep(I8Const<3>{}, f1a, f1b, f0a, f0b);
         }
     };
     const unsigned smem_base = (unsigned)(size_t)(const __attribute__((address_space(3))) char *)smem;
@@ -271,22 +319,29 @@ __global__ __launch_bounds__(512, 2) void k_coarse_top2_i8(CoarseArgs a)
         for (int t = 0; t < nT; ++t, ++done) {
             stage_next();
             const int ahead = staged - done - 1;   // tiles issued after the one about to be read
-            if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NG) : "memory");
-            else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NG) : "memory");
+            if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NINST) : "memory");
+            else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NINST) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             const unsigned tile = smem_base + (done % RCN_NBUF) * BUFB;
-            const unsigned hnl = tile + TILEB + w * (BT * 4);
             const unsigned base = (unsigned)(t * BT);
+            if constexpr (SH == 0) {
+                const unsigned hnl = tile + TILEB;
 #pragma unroll
-            for (int rb = 0; rb < BT / 32; rb += 2) {
-                if constexpr (SH == 0) {
+                for (int rb = 0; rb < BT / 32; rb += 2) {
                     step(pX0, pX1, pY0, pY1, tile, hnl, rb, base + 32u * rb - 32u);   // epilogue of the row block before (t, rb)
                     step(pY0, pY1, pX0, pX1, tile, hnl, rb + 1, base + 32u * rb);     // epilogue of (t, rb)
-                } else {
-                    step16(qX, qY, tile, hnl, rb, base + 32u * rb - 32u);
-                    step16(qY, qX, tile, hnl, rb + 1, base + 32u * rb);
                 }
+            } else {
+                static_assert(BT / 32 == 4, "four row blocks per tile are spelled out");
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) fb[ks] = tile + fl[ks];
+                hb = tile + hl;
+                u32x4 oA[4], oB[4];
+                step16(I8Const<0>{}, qX, qY, oA, oB, base - 32u);
+                step16(I8Const<1>{}, qY, qX, oB, oA, base);
+                step16(I8Const<2>{}, qX, qY, oA, oB, base + 32u);
+                step16(I8Const<3>{}, qY, qX, oB, oA, base + 64u);
             }
         }
         if (ABL & 1) {

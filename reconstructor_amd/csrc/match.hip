@@ -43,6 +43,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define RCN_I8_IDX_MASK ((1u << RCN_I8_IDX_BITS) - 1u)
 #define RCN_I8_PAD_ACC ((1 << (32 - RCN_I8_IDX_BITS)) - 1)   // accumulator of a padded train row: ranks last, fits the key
 #define RCN_I8_BT 128                                   // train rows per LDS tile
+#ifndef RCN_I8_EARLY_OPEN
+#define RCN_I8_EARLY_OPEN 1                             // a row block's opening LDS reads go out in the last k-step of the block before (0: timing only)
+#endif
 #define RCN_I8_RES_MAX 8.01                             // |s x - xq| <= sqrt(256) / 2 for a row inside the grid, with room for its rounding up
 #define RCN_I8_M_MAX 720.0                              // largest s Nmax + 8.5 for which every accumulator fits the key (fix_scale)
 #define RCN_I8_PEAK_MAX 8.0                             // int8 only when max |x| sqrt(D) / Nmax is below this (fix_scale)
@@ -2462,7 +2465,7 @@ template <int DP, int ABL = 0, int SH = 0> static hipError_t launch_coarse(rcn_c
 
 template <int ABL, int SH> static hipError_t launch_coarse_i8(rcn_ctx *ctx, const CoarseArgs &ca, int blocks)
 {
-    const size_t lds = (size_t)RCN_NBUF * (RCN_I8_BT * 256 + 8 * RCN_I8_BT * 4) + RCN_TBL_BYTES;
+    const size_t lds = (size_t)RCN_NBUF * i8addr::BUF_BYTES + RCN_TBL_BYTES;   // tile + ONE half-norm image per ring buffer
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_coarse_top2_i8<ABL, SH>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
