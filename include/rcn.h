@@ -50,9 +50,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * correspondence search and the attach entry points; 5 -> 6 added coarse_dtype to rcn_match_stats; 6 -> 7 the two-view
  * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options;
  * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*; 10 -> 11 the robust losses rcn_ba_solve_robust, rcn_ba_session_set_loss,
- * rcn_ba_session_loss_report).
+ * rcn_ba_session_loss_report; 11 -> 12 constant cameras and the local adjustment: rcn_ba_solve_constant, rcn_ba_session_solve_local,
+ * rcn_ba_session_covisible, rcn_ba_session_local_seconds).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 11
+#define RCN_ABI_REVISION 12
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -584,6 +585,16 @@ typedef struct {
 int rcn_ba_solve_robust(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options, const rcn_ba_loss *loss,
                         rcn_ba_summary *summary, rcn_ba_loss_report *report, double *weights_host);
 
+/* Constant cameras.  cam_constant: n_cams bytes; a camera with a non-zero byte has no tangent column at all -- no pose columns and, in
+ * intrinsics_mode 1, no intrinsics columns: its observations are residuals of their landmarks alone, its pose6 / intr6 come back
+ * unchanged bit for bit, its focal lengths are neither projected onto focal_upper_bound nor counted in bound_projections.
+ * fix_cam0_pose / fix_cam1_translation keep their meaning for cameras 0 and 1 when those are not constant.  ONE constant camera fixes
+ * position and orientation but leaves the scale free (rcn_ba_options' default holds camera 1's translation for that); two or more fix
+ * the gauge.  cam_constant == NULL or all zeros: rcn_ba_solve_robust, bit for bit.  RCN_ERR_ARG with a message when no parameter of
+ * the reduced system is left free (every camera constant). */
+int rcn_ba_solve_constant(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options, const rcn_ba_loss *loss,
+                          const uint8_t *cam_constant, rcn_ba_summary *summary, rcn_ba_loss_report *report, double *weights_host);
+
 /* Introspection, pure host code (no device, no ctx): the SCHEDULE of the dense factorisation inside rcn_ba_solve for a reduced system of
  * n_blocks 128-row blocks (csrc/chol_plan.h) -- the list of tile operations in an order that is a correct sequential algorithm, each
  * with its stream and the device counters it waits for, and the tile maps of the pipelined launches.  tests/test_chol_plan.py executes
@@ -627,6 +638,28 @@ int  rcn_ba_session_counts(const rcn_ba_session *s, int32_t *n_cams, int32_t *n_
 int  rcn_ba_session_graph(rcn_ba_session *s, int32_t *pt_out, int32_t *cam_out, int32_t *xy_out);
 /* options == NULL: rcn_ba_default_options for the current camera count (the reference's choice, BundleAdjuster.cpp:99-142) */
 int  rcn_ba_session_solve(rcn_ba_session *s, const rcn_ba_options *options, rcn_ba_summary *summary);
+/* Local adjustment (COLMAP's AdjustLocalBundle): the cameras free_cams move, together with every landmark that has an observation in
+ * one of them; every other camera that sees such a landmark takes part as a constant (rcn_ba_solve_constant); every other landmark
+ * has no residual in the sub-problem and stays where it is, bit for bit, and so does every camera that is not free.  The sub-problem
+ * is cut out of the resident arrays on the device (landmarks in session order, observations in track order, cameras in ascending
+ * session index), solved under the session's loss, and scattered back; the graph and its version do not change.
+ * free_cams: n_free distinct session camera indices, any order.  options == NULL: rcn_ba_default_options(n_free)
+ * (a local bundle of < 10 views keeps all intrinsics constant, like the reference's small problems); fix_cam0_pose /
+ * fix_cam1_translation apply to the sub-problem's cameras 0 and 1 when those are free.
+ * info_out (may be NULL): local cameras, of them constant, landmarks, observations of the sub-problem.
+ * RCN_ERR_ARG with a message: a null or empty free_cams, an index out of range, a duplicate, free cameras without any observation
+ * (no free parameter); the session is unchanged and usable. */
+int  rcn_ba_session_solve_local(rcn_ba_session *s, const int32_t *free_cams, int32_t n_free,
+                                const rcn_ba_options *options, rcn_ba_summary *summary, int32_t info_out[4]);
+/* Landmarks shared with camera `cam`, per session camera (counts_out[n_cams], counts_out[cam] = its own landmark
+ * count), and the k cameras other than `cam` that share the most, count descending, ties to the lower index;
+ * fewer than k when fewer share any.  A landmark that sees a camera twice counts once for it.  Integer counts on the device; the
+ * selection among n_cams numbers on the host.  counts_out may be NULL; cams_out / n_out may be NULL when k == 0.
+ * RCN_ERR_ARG with a message: cam out of range, k < 0. */
+int  rcn_ba_session_covisible(rcn_ba_session *s, int32_t cam, int32_t k, int32_t *cams_out, int32_t *n_out, int32_t *counts_out);
+/* Host-clock seconds of the last rcn_ba_session_solve_local, each part ending synchronised: the extraction, the solve (structure pass
+ * and workspace included; rcn_ba_summary::solve_seconds is the LM loop inside it), the scatter.  For tools/ba_local_timing.py. */
+int  rcn_ba_session_local_seconds(const rcn_ba_session *s, double seconds_out[3]);
 /* The loss of every later rcn_ba_session_solve (kept across solves; NULL or RCN_BA_LOSS_TRIVIAL: none): rcn_ba_solve_robust's
  * arithmetic on the same problem, bit for bit.  Argument errors as there. */
 int  rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss);

@@ -19,7 +19,7 @@ SYMBOLS = [
     "rcn_create", "rcn_destroy", "rcn_last_error", "rcn_version", "rcn_set_stream",
     "rcn_synchronize", "rcn_desc_upload", "rcn_desc_upload_device", "rcn_desc_upload_batch_device", "rcn_desc_upload_batch", "rcn_desc_remove", "rcn_desc_sample_device", "rcn_desc_sample_errors", "rcn_desc_sample_batch_device", "rcn_desc_clear",
     "rcn_desc_count", "rcn_match_pair", "rcn_match_grid", "rcn_match_grid_device",
-    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_solve_robust", "rcn_ba_factor_plan",
+    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_solve_robust", "rcn_ba_solve_constant", "rcn_ba_factor_plan",
     "rcn_landmark_validity", "rcn_landmark_validity_device",
     "rcn_fmat_filter", "rcn_fmat_filter_grid", "rcn_fmat_filter_grid_device",
     "rcn_coords_upload", "rcn_coords_upload_batch", "rcn_coords_clear", "rcn_match_table_filter_device",
@@ -32,6 +32,7 @@ SYMBOLS = [
     "rcn_ba_session_add_points", "rcn_ba_session_add_observations", "rcn_ba_session_counts", "rcn_ba_session_graph",
     "rcn_ba_session_solve", "rcn_ba_session_set_loss", "rcn_ba_session_loss_report", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
     "rcn_ba_session_remove_outliers", "rcn_ba_session_triangulate",
+    "rcn_ba_session_solve_local", "rcn_ba_session_covisible", "rcn_ba_session_local_seconds",
     "rcn_triangulate", "rcn_triangulate_device",
     "rcn_match_lists_upload", "rcn_match_lists_clear", "rcn_corr_set_workspace_bytes", "rcn_corr_2d3d", "rcn_corr_2d3d_device",
     "rcn_landmark_attach", "rcn_ba_session_attach",
@@ -409,6 +410,14 @@ def load():
     L.rcn_shard_profile.argtypes = [vp, C.c_int]
     L.rcn_shard_profile_read.restype = C.c_int
     L.rcn_shard_profile_read.argtypes = [vp, C.POINTER(ShardTimes)]
+    L.rcn_ba_solve_constant.restype = C.c_int
+    L.rcn_ba_solve_constant.argtypes = [vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaLoss), vp, C.POINTER(BaSummary), C.POINTER(BaLossReport), vp]
+    L.rcn_ba_session_solve_local.restype = C.c_int
+    L.rcn_ba_session_solve_local.argtypes = [vp, vp, i32, C.POINTER(BaOptions), C.POINTER(BaSummary), vp]
+    L.rcn_ba_session_covisible.restype = C.c_int
+    L.rcn_ba_session_covisible.argtypes = [vp, i32, i32, vp, C.POINTER(i32), vp]
+    L.rcn_ba_session_local_seconds.restype = C.c_int
+    L.rcn_ba_session_local_seconds.argtypes = [vp, vp]
     L.rcn_ba_session_create.restype = C.c_int
     L.rcn_ba_session_create.argtypes = [vp, C.POINTER(vp)]
     L.rcn_ba_session_destroy.restype = None

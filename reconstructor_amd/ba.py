@@ -45,8 +45,11 @@ def loss_report_dict(r):
     return {k: getattr(r, k) for k, _ in r._fields_}
 
 
-def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=None, allow_failure=False, loss=None, report=False):
+def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=None, allow_failure=False, loss=None, report=False,
+               constant=None):
     """Returns (poses, intrinsics, points, summary); inputs are copied, not modified.
+    constant: None or a mask over the cameras (rcn_ba_solve_constant): a camera with a true entry has no free parameter and comes
+    back unchanged bit for bit.
     allow_failure: a solve that ends in RCN_BA_FAILURE (RCN_ERR_NUMERIC; the summary is filled) returns instead of raising.
     loss: None (rcn_ba_solve) or what make_loss takes (rcn_ba_solve_robust: Huber, soft-L1 or Cauchy with a scale in pixels; the
     summary's costs are then robust costs).  report: the summary also carries "loss_report" (rcn_ba_loss_report as a dict) and
@@ -63,7 +66,16 @@ def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=
                         pt.ctypes.data if pt.size else None)
     o = options if options is not None else default_options(ctx, poses.shape[0])
     s = _lib.BaSummary()
-    if loss is None and not report:
+    if constant is not None:
+        mask = np.ascontiguousarray(np.asarray(constant) != 0, np.uint8)
+        if mask.shape != (poses.shape[0],):
+            raise ValueError("solve_flat: constant must hold one entry per camera")
+        ls = make_loss(loss)
+        rep = _lib.BaLossReport()
+        w = np.zeros(max(cam.shape[0], 1))
+        rc = ctx.lib.rcn_ba_solve_constant(ctx.h, C.byref(pb), C.byref(o), C.byref(ls) if ls is not None else None, mask.ctypes.data,
+                                           C.byref(s), C.byref(rep) if report else None, w.ctypes.data if report else None)
+    elif loss is None and not report:
         rc = ctx.lib.rcn_ba_solve(ctx.h, C.byref(pb), C.byref(o), C.byref(s))
     else:
         ls = make_loss(loss)
@@ -79,9 +91,9 @@ def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=
     return poses, intr, pts, d
 
 
-def solve_scene(ctx, scene, options=None, allow_failure=False, loss=None, report=False):
+def solve_scene(ctx, scene, options=None, allow_failure=False, loss=None, report=False, constant=None):
     return solve_flat(ctx, scene["poses"], scene["intrinsics"], scene["points"], scene["obs_uv"],
-                      scene["obs_cam"], scene["obs_pt"], options, allow_failure, loss, report)
+                      scene["obs_cam"], scene["obs_pt"], options, allow_failure, loss, report, constant)
 
 
 def _rot_to_angle_axis(R):
@@ -230,6 +242,31 @@ class BaSession:
         self.ctx.check(self.ctx.lib.rcn_ba_session_solve(self.h, C.byref(options) if options is not None else None, C.byref(s)))
         return summary_dict(s)
 
+    def solve_local(self, free_cams, options=None):
+        """Local adjustment (rcn_ba_session_solve_local): the cameras free_cams and the landmarks they see move, every other camera that
+        sees one of those landmarks is constant, everything else stays.  Returns (summary, info) with info = dict(n_cams, n_constant,
+        n_points, n_obs) of the sub-problem."""
+        fc = np.ascontiguousarray(free_cams, np.int32).reshape(-1)
+        s = _lib.BaSummary()
+        info = np.zeros(4, np.int32)
+        self.ctx.check(self.ctx.lib.rcn_ba_session_solve_local(self.h, fc.ctypes.data if len(fc) else None, len(fc),
+                                                               C.byref(options) if options is not None else None, C.byref(s), info.ctypes.data))
+        return summary_dict(s), dict(zip(("n_cams", "n_constant", "n_points", "n_obs"), (int(v) for v in info)))
+
+    def local_seconds(self):
+        """(extraction, solve, scatter) host-clock seconds of the last solve_local"""
+        t = np.zeros(3)
+        self.ctx.check(self.ctx.lib.rcn_ba_session_local_seconds(self.h, t.ctypes.data))
+        return tuple(float(v) for v in t)
+
+    def covisible(self, cam, k):
+        """(the k cameras that share the most landmarks with `cam`, count descending, ties to the lower index -- fewer when fewer
+        share any; landmarks shared with `cam` per session camera, [cam] = its own landmark count)  (rcn_ba_session_covisible)"""
+        nc = self.counts()[0]
+        cams, counts, n = np.zeros(max(int(k), 1), np.int32), np.zeros(max(nc, 1), np.int32), C.c_int32()
+        self.ctx.check(self.ctx.lib.rcn_ba_session_covisible(self.h, int(cam), int(k), cams.ctypes.data, C.byref(n), counts.ctypes.data))
+        return cams[:n.value].copy(), counts[:nc]
+
     def set_loss(self, loss):
         """the loss of every later solve (rcn_ba_session_set_loss): None switches it off"""
         ls = make_loss(loss)
@@ -364,3 +401,34 @@ def smoke(ctx):
     P, I, X, s = solve_scene(ctx, sc)
     assert s["final_rms_px"] < 1.0 < s["initial_rms_px"], s
     return sc, (P, I, X, s)
+
+
+def smoke_local(ctx):
+    """A local adjustment on the GPU: the last camera of a 12-camera session and the three that share the most landmarks with it are
+    freed, the sub-problem is cut out on the device, solved with the other cameras constant and scattered back.  Checked against
+    itself: the cost falls, the cameras outside the window and the landmarks the window does not see keep their bits."""
+    from . import synth_ba
+    sc = synth_ba.make_scene(12, 300, obs_per_point=4, seed=5)
+    ses = BaSession(ctx)
+    try:
+        for p, k in zip(sc["poses"], sc["intrinsics"]):
+            ses.add_camera(p, k)
+        ses.add_points(sc["points"])
+        ses.add_observations(sc["obs_pt"], sc["obs_cam"], sc["obs_uv"].astype(np.int32))
+        near, counts = ses.covisible(11, 3)
+        free = np.concatenate([[11], near])
+        P0, X0 = ses.cameras()[0], ses.points()
+        o = default_options(ctx, len(free))
+        o.fix_cam0_pose = o.fix_cam1_translation = 0
+        s, info = ses.solve_local(free, o)
+        P1, X1 = ses.cameras()[0], ses.points()
+        held = np.setdiff1d(np.arange(12), free)
+        seen = np.zeros(300, bool)
+        seen[sc["obs_pt"][np.isin(sc["obs_cam"], free)]] = True
+        assert len(near) == 3 and counts[11] == (sc["obs_cam"] == 11).sum()
+        assert s["final_cost"] < s["initial_cost"] and info["n_points"] == seen.sum() and info["n_constant"] == info["n_cams"] - 4, (s, info)
+        assert P1[held].tobytes() == P0[held].tobytes() and X1[~seen].tobytes() == X0[~seen].tobytes() and (~seen).any()
+        assert not np.array_equal(P1[free], P0[free]) and not np.array_equal(X1[seen], X0[seen])
+        return info, s
+    finally:
+        ses.close()

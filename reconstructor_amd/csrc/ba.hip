@@ -1271,7 +1271,7 @@ __global__ __launch_bounds__(256) void k_ba_plus(BaDev d, double alpha, double *
         // intrinsics when they are all held) or one no residual uses is not part of the state; a block with a
         // subset manifold counts with all six coordinates
         const bool used = d.cam_obs_off[c + 1] > d.cam_obs_off[c];
-        const bool pose_in = used && dc > 0 && d.cols[10 * c] < 6, intr_in = used && d.mode == 1;
+        const bool pose_in = used && dc > 0 && d.cols[10 * c] < 6, intr_in = used && d.mode == 1 && dc > 0;      // (dc == 0 in mode 1: a constant camera)
         for (int k = 0; k < 6; ++k) {
             ps[k] = d.poses[6 * c + k]; in[k] = d.intr[6 * c + k];
             if (pose_in) xn += ps[k] * ps[k];
@@ -1462,6 +1462,14 @@ int rcn_ba_solve_robust(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_opt
     return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr, loss, report, weights_host);
 }
 
+int rcn_ba_solve_constant(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, const rcn_ba_loss *loss, const uint8_t *cam_constant,
+                          rcn_ba_summary *sum, rcn_ba_loss_report *report, double *weights_host)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr, loss, report, weights_host, cam_constant);
+}
+
 }  // extern "C"
 
 // The loss as the kernels take it.  NULL: no loss, and a report counts nothing beyond the scale (b = inf).
@@ -1517,8 +1525,11 @@ int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const 
 // lists of the Schur build are reused when the token says the graph has not changed since they were built.
 // loss != nullptr with a non-trivial kind: the two kernels that evaluate observations run in their robust form (k_ba_eval<JAC, true>,
 // k_ba_dirgrad<true>); nothing else in the loop changes.  report / weights_host: one pass over the observations at the final point.
+// cam_constant != nullptr (n_cams bytes): a camera with a non-zero byte has no tangent column at all (cam_dim = 0, in intrinsics mode 1
+// too) -- its observations are residuals of the landmarks alone, its 12 numbers come back as they went in.  The kernels read the
+// tables, so nothing but the tables (and the three places marked "constant camera" below) knows of it.
 int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
-                     const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host)
+                     const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host, const uint8_t *cam_constant)
 {
     if (!pb || !opt || !sum || pb->n_cams <= 0 || pb->n_points < 0 || pb->n_obs < 0 || !pb->poses ||
         !pb->intrinsics || (pb->n_points > 0 && !pb->points && !res) ||
@@ -1556,14 +1567,16 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     for (int j = 0; j < np; ++j) kmax = std::max(kmax, pt_off[j + 1] - pt_off[j]);
     for (int c = 0; c < nc; ++c) {
         int dcm = 0;
-        if (!(c == 0 && opt->fix_cam0_pose)) {
+        const bool constant = cam_constant && cam_constant[c];      // constant camera: no column, whatever the options say
+        if (!constant && !(c == 0 && opt->fix_cam0_pose)) {
             const int npose = (c == 1 && opt->fix_cam1_translation) ? 3 : 6;
             for (int k = 0; k < npose; ++k) cols[10 * c + dcm++] = k;
         }
-        if (opt->intrinsics_mode == 1) { cols[10 * c + dcm++] = 6; cols[10 * c + dcm++] = 7; cols[10 * c + dcm++] = 10; cols[10 * c + dcm++] = 11; }
+        if (!constant && opt->intrinsics_mode == 1) { cols[10 * c + dcm++] = 6; cols[10 * c + dcm++] = 7; cols[10 * c + dcm++] = 10; cols[10 * c + dcm++] = 11; }
         cam_off[c] = n; cam_dim[c] = dcm; n += dcm;
     }
     cam_off[nc] = n;
+    if (n == 0) { ctx->set_error("rcn_ba_solve: the reduced system has no free parameter (every camera is constant)"); return RCN_ERR_ARG; }
     const int npad = std::max(chol::BLOCK, (n + chol::BLOCK - 1) / chol::BLOCK * chol::BLOCK), nblk = npad / chol::BLOCK;
     sum->reduced_dim = n;
 
@@ -1628,8 +1641,8 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     std::vector<double> intr0(pb->intrinsics, pb->intrinsics + 6 * (size_t)nc);
     if (opt->intrinsics_mode == 1)
         for (int c = 0; c < nc; ++c)
-            for (int k = 0; k < 2; ++k)
-                if (intr0[6 * c + k] > opt->focal_upper_bound) { intr0[6 * c + k] = opt->focal_upper_bound; sum->bound_projections++; }
+            for (int k = 0; k < 2; ++k)      // (cam_dim == 0 in mode 1: a constant camera, not part of the box)
+                if (cam_dim[c] > 0 && intr0[6 * c + k] > opt->focal_upper_bound) { intr0[6 * c + k] = opt->focal_upper_bound; sum->bound_projections++; }
     RCN_HIP(H2D(d.intr, intr0.data(), sizeof(double) * 6 * nc));
     if (res) {
         if (np > 0) RCN_HIP(hipMemcpyAsync(d.pts, res->pts, sizeof(double) * 3 * np, hipMemcpyDeviceToDevice, st));

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <climits>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <unordered_map>
 
@@ -80,6 +81,10 @@ struct rcn_ba_session {
     bool have_inlier = false;
     rcn_ba_loss loss{RCN_BA_LOSS_TRIVIAL, 0, 0.0};   // rcn_ba_session_set_loss: the loss of every later solve (trivial: none)
     DevBuf cams_dev;                                 // rcn_ba_session_loss_report: the cameras' 6 + 6 numbers, uploaded per call
+    BaLocalWs loc;                                   // rcn_ba_session_solve_local / _covisible: the sub-problem's arrays (ba_local.hip)
+    std::vector<double> loc_poses, loc_intr;         // ... its cameras' 6 + 6 numbers
+    std::vector<uint8_t> loc_free, loc_const;        // ... free per session camera, constant per local camera
+    double loc_seconds[3] = {0.0, 0.0, 0.0};         // the last local solve: extraction, rcn_int_ba_solve, scatter (host clock; each ends synchronised)
 };
 
 #define SES_HIP(call)                                                                    \
@@ -152,6 +157,7 @@ void rcn_ba_session_destroy(rcn_ba_session *s)
         DevBuf *bufs[] = {&s->uv, &s->ocam, &s->opt, &s->xy, &s->pt_off, &s->poses34, &s->intr_dev, &s->inl, &s->keep, &s->cnt, &s->idx, &s->tmp_pts,
                           &s->t_in, &s->t_xyz, &s->t_ws, &s->g_in, &s->cams_dev};
         for (DevBuf *b : bufs) b->release();
+        s->loc.release();
     }
     delete s;
 }
@@ -254,6 +260,107 @@ int rcn_ba_session_solve(rcn_ba_session *s, const rcn_ba_options *options, rcn_b
     s->have_inlier = false;
     return rcn_int_ba_solve(ctx, &pb, &o, summary, &res,     // poses / intrinsics come back into the host mirror, points stay in HBM
                             s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr);
+}
+
+// A local adjustment: the cameras free_cams[] move, with the landmarks they see; every other camera that sees one of those landmarks
+// takes part as a constant, every other landmark stays where it is (ba_local.hip).  The sub-problem goes through rcn_int_ba_solve
+// like a session's global problem -- resident arrays, the session's loss -- with the constant mask and no pair-list token: lists of a
+// sub-problem are never taken for cached, and the ctx's token ends up 0, so the next global solve rebuilds its own.
+int rcn_ba_session_solve_local(rcn_ba_session *s, const int32_t *free_cams, int32_t n_free, const rcn_ba_options *options,
+                               rcn_ba_summary *summary, int32_t info_out[4])
+{
+    if (!s || !summary) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    const char *who = "rcn_ba_session_solve_local";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (info_out) std::fill(info_out, info_out + 4, 0);
+    if (!free_cams || n_free <= 0) { ctx->set_error(std::string(who) + ": no free camera"); return RCN_ERR_ARG; }
+    s->loc_free.assign((size_t)nc, 0);
+    for (int32_t k = 0; k < n_free; ++k) {
+        const int32_t c = free_cams[k];
+        if (c < 0 || c >= nc) { ctx->set_error(std::string(who) + ": camera index out of range"); return RCN_ERR_ARG; }
+        if (s->loc_free[c]) { ctx->set_error(std::string(who) + ": camera " + std::to_string(c) + " is listed twice"); return RCN_ERR_ARG; }
+        s->loc_free[c] = 1;
+    }
+    SES_HIP(hipSetDevice(ctx->device));
+    int rc = sync_observations(s);
+    if (rc) return rc;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    BaLocalWs &w = s->loc;
+    rc = rcn_int_ba_local_extract(ctx, w, nc, np, (int32_t)s->n_obs, static_cast<const double *>(s->pts.p), s->uv.as<double>(), s->ocam.as<int32_t>(),
+                                  s->pt_off.as<int32_t>(), s->loc_free.data());
+    if (rc) return rc;
+    const double t1 = now();
+    if (w.n_points == 0) { ctx->set_error(std::string(who) + ": the free cameras have no observation: the reduced system has no free parameter"); return RCN_ERR_ARG; }
+    const int32_t ncl = w.n_cams;
+    s->loc_poses.resize(6 * (size_t)ncl); s->loc_intr.resize(6 * (size_t)ncl); s->loc_const.resize((size_t)ncl);
+    int32_t n_const = 0;
+    for (int32_t l = 0; l < ncl; ++l) {
+        const int32_t c = w.h_cam_map[l];
+        if (c < 0 || c >= nc || (l && c <= w.h_cam_map[l - 1])) { ctx->set_error(std::string(who) + ": camera map out of order"); return RCN_ERR_HIP; }
+        std::copy(s->poses.begin() + 6 * (size_t)c, s->poses.begin() + 6 * (size_t)c + 6, s->loc_poses.begin() + 6 * (size_t)l);
+        std::copy(s->intr.begin() + 6 * (size_t)c, s->intr.begin() + 6 * (size_t)c + 6, s->loc_intr.begin() + 6 * (size_t)l);
+        s->loc_const[l] = s->loc_free[c] ? 0 : 1;
+        n_const += s->loc_const[l];
+    }
+    if (info_out) { info_out[0] = ncl; info_out[1] = n_const; info_out[2] = w.n_points; info_out[3] = w.n_obs; }
+    rcn_ba_options o;
+    if (options) o = *options;
+    else rcn_ba_default_options(n_free, &o);                  // a local bundle of < 10 views keeps all intrinsics constant
+    rcn_ba_problem pb{ncl, w.n_points, w.n_obs, 0, s->loc_poses.data(), s->loc_intr.data(), nullptr,
+                      s->h_uv.data(), w.h_ocam.data(), w.h_opt.data()};      // (obs_uv: the solver reads the resident copy; the pointer only has to be there)
+    BaResident res{w.pts.as<double>(), w.uv.as<double>(), w.ocam.as<int>(), w.opt.as<int>(), 0};
+    s->have_inlier = false;
+    rc = rcn_int_ba_solve(ctx, &pb, &o, summary, &res, s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr, nullptr, nullptr, s->loc_const.data());
+    if (rc != RCN_OK && rc != RCN_ERR_NUMERIC) return rc;     // (a failed solve has still written its last accepted point, as rcn_ba_session_solve leaves it)
+    const double t2 = now();
+    const int rcs = rcn_int_ba_local_scatter(ctx, w, static_cast<double *>(s->pts.p));
+    if (rcs) return rcs;
+    for (int32_t l = 0; l < ncl; ++l) {
+        if (s->loc_const[l]) continue;
+        const int32_t c = w.h_cam_map[l];
+        std::copy(s->loc_poses.begin() + 6 * (size_t)l, s->loc_poses.begin() + 6 * (size_t)l + 6, s->poses.begin() + 6 * (size_t)c);
+        std::copy(s->loc_intr.begin() + 6 * (size_t)l, s->loc_intr.begin() + 6 * (size_t)l + 6, s->intr.begin() + 6 * (size_t)c);
+    }
+    s->loc_seconds[0] = t1 - t0; s->loc_seconds[1] = t2 - t1; s->loc_seconds[2] = now() - t2;
+    return rc;
+}
+
+int rcn_ba_session_local_seconds(const rcn_ba_session *s, double seconds_out[3])
+{
+    if (!s || !seconds_out) return RCN_ERR_ARG;
+    std::copy(s->loc_seconds, s->loc_seconds + 3, seconds_out);
+    return RCN_OK;
+}
+
+int rcn_ba_session_covisible(rcn_ba_session *s, int32_t cam, int32_t k, int32_t *cams_out, int32_t *n_out, int32_t *counts_out)
+{
+    if (!s) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    const char *who = "rcn_ba_session_covisible";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (n_out) *n_out = 0;
+    if (cam < 0 || cam >= nc) { ctx->set_error(std::string(who) + ": camera index out of range"); return RCN_ERR_ARG; }
+    if (k < 0) { ctx->set_error(std::string(who) + ": k is negative"); return RCN_ERR_ARG; }
+    if (k > 0 && (!cams_out || !n_out)) { ctx->set_error(std::string(who) + ": no room for the cameras"); return RCN_ERR_ARG; }
+    SES_HIP(hipSetDevice(ctx->device));
+    int rc = sync_observations(s);
+    if (rc) return rc;
+    std::vector<int32_t> counts((size_t)nc);
+    rc = rcn_int_ba_local_covisible(ctx, s->loc, nc, np, s->ocam.as<int32_t>(), s->pt_off.as<int32_t>(), cam, counts.data());
+    if (rc) return rc;
+    if (counts_out) std::copy(counts.begin(), counts.end(), counts_out);
+    // the selection among n_cams numbers: count descending, ties to the lower index
+    std::vector<int32_t> order;
+    for (int32_t c = 0; c < nc; ++c) if (c != cam && counts[c] > 0) order.push_back(c);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return counts[a] > counts[b]; });
+    const int32_t n = std::min<int32_t>(k, (int32_t)order.size());
+    for (int32_t i = 0; i < n; ++i) cams_out[i] = order[i];
+    if (n_out) *n_out = n;
+    return RCN_OK;
 }
 
 int rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss)

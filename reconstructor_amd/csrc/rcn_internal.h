@@ -324,7 +324,23 @@ struct BaResident {
     uint64_t pair_token;          // identifies (session, graph version): pair lists built under the same token are reused
 };
 int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
-                     const rcn_ba_loss *loss = nullptr, rcn_ba_loss_report *report = nullptr, double *weights_host = nullptr);
+                     const rcn_ba_loss *loss = nullptr, rcn_ba_loss_report *report = nullptr, double *weights_host = nullptr,
+                     const uint8_t *cam_constant = nullptr);
+// ba_local.hip, ctx->mu held: the sub-problem of a local adjustment cut out of a session's resident arrays (rcn_ba_session_solve_local), the
+// scatter of its solved points, and the covisibility counts (rcn_ba_session_covisible).  The workspace belongs to the session; it only grows.
+struct BaLocalWs {
+    DevBuf flags, ints;                              // free / selected bytes; counts, camera flags, the three scans, the sizes
+    DevBuf pts, uv, ocam, opt, pt_map, cam_map;      // the compacted sub-problem and its local -> session maps
+    DevBuf counts;                                   // covisibility counts
+    std::vector<int32_t> h_ocam, h_opt, h_cam_map;   // the sub-problem's structure on the host (what rcn_int_ba_solve validates and counts)
+    int32_t n_cams = 0, n_points = 0, n_obs = 0;     // sizes of the last extraction
+    size_t last_obs = 0;                             // ... its observations, as the next extraction's guess for the copy back
+    void release();
+};
+int rcn_int_ba_local_extract(rcn_ctx *ctx, BaLocalWs &w, int32_t nc, int32_t np, int32_t no, const double *pts, const double *uv,
+                             const int32_t *ocam, const int32_t *pt_off, const uint8_t *free_host);
+int rcn_int_ba_local_scatter(rcn_ctx *ctx, BaLocalWs &w, double *pts);
+int rcn_int_ba_local_covisible(rcn_ctx *ctx, BaLocalWs &w, int32_t nc, int32_t np, const int32_t *ocam, const int32_t *pt_off, int32_t cam, int32_t *counts_host);
 // ba.hip, ctx->mu held: the argument check of a loss (NULL: none); the loss's report at a point whose arrays are all in HBM
 int rcn_int_ba_loss_check(rcn_ctx *ctx, const rcn_ba_loss *loss, const char *who, int *kind, double *a, double *b);
 int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const double *intr_dev, const double *pts_dev, const double *uv_dev,

@@ -11,6 +11,7 @@
 // If the containers changed in any other way (a landmark or an observation erased by removeOutlierLandmarks, a
 // landmark moved, the view order permuted) the session is rebuilt from the containers; rebuilds() counts that.
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -55,6 +56,79 @@ public:
                                         std::unordered_map<int, Pose4> &imgIdx2camPose,
                                         std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics,
                                         std::vector<int> imgIdxOrder)
+    {
+        std::unordered_map<int, int> global2local = sync(features, landmarks, imgIdx2camPose, imgIdx2camIntrinsics, imgIdxOrder);
+
+        const int rc = rcn_ba_session_solve(session_, nullptr, &summary);       // default options: BundleAdjuster.cpp:99-142
+        if (rc != RCN_OK && rc != RCN_ERR_NUMERIC)                              // the reference ignores Ceres' summary (:145-147)
+            throw std::runtime_error(std::string("rcn_ba_session_solve: ") + rcn_last_error(ctx_));
+        writeBack(landmarks, imgIdx2camPose, imgIdx2camIntrinsics, imgIdxOrder, nullptr);
+        return global2local;
+    }
+
+    // A LOCAL adjustment after registering newImgIdx (COLMAP's AdjustLocalBundle; rcn_ba_session_solve_local): the new view and the
+    // windowSize views that share the most landmarks with it move, with the landmarks they see; every other view that sees one of those
+    // landmarks is held constant, everything else is left alone.  The containers are diffed into the session exactly as adjust does it.
+    // While the window covers every registered view this IS adjust (a global solve, the reference's options).  Otherwise the options are
+    // rcn_ba_default_options(views in the window) with nothing held by index -- the constant views fix the gauge --, so a window of
+    // fewer than 10 views keeps all intrinsics constant.  The first two registered views are never freed with a window (the new view aside):
+    // every global adjust holds the pose of the first and the translation of the second (BundleAdjuster.cpp:100-105), which is what pins
+    // the reconstruction's frame and scale; a local adjustment that moved them would move the frame under the next global one, and the two
+    // kinds of adjust would no longer minimise over the same constants.  Written back: the landmarks, and the window's poses and intrinsics only (the
+    // matrices of the other views are not touched, so they do not pass through the unpack of BundleAdjuster.cpp:157-185).
+    // lastWindow(): the image indices that were free; localInfo: rcn_ba_session_solve_local's info_out (zeros after a global solve).
+    template <class Pose4>
+    std::unordered_map<int, int> adjustLocal(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                                             std::vector<Landmark> &landmarks,
+                                             std::unordered_map<int, Pose4> &imgIdx2camPose,
+                                             std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics,
+                                             std::vector<int> imgIdxOrder, int newImgIdx, int windowSize)
+    {
+        const int nCams = (int)imgIdxOrder.size();
+        std::unordered_map<int, int> global2local = sync(features, landmarks, imgIdx2camPose, imgIdx2camIntrinsics, imgIdxOrder);
+        auto it = global2local.find(newImgIdx);
+        if (it == global2local.end() || windowSize < 0) throw std::runtime_error("IncrementalBundleAdjuster::adjustLocal: the new view is not registered, or a negative window");
+        std::vector<int32_t> freeCams(1 + (size_t)windowSize, it->second);
+        int32_t nNear = 0;
+        check(rcn_ba_session_covisible(session_, it->second, windowSize, freeCams.data() + 1, &nNear, nullptr), "rcn_ba_session_covisible");
+        freeCams.resize(1 + (size_t)nNear);
+        window_.clear();
+        for (int32_t c : freeCams) window_.push_back(imgIdxOrder[c]);
+        for (int k = 0; k < 4; ++k) localInfo[k] = 0;
+        int rc;
+        if ((int)freeCams.size() >= nCams) {
+            rc = rcn_ba_session_solve(session_, nullptr, &summary);
+            if (rc != RCN_OK && rc != RCN_ERR_NUMERIC) throw std::runtime_error(std::string("rcn_ba_session_solve: ") + rcn_last_error(ctx_));
+            writeBack(landmarks, imgIdx2camPose, imgIdx2camIntrinsics, imgIdxOrder, nullptr);
+            return global2local;
+        }
+        freeCams.erase(std::remove_if(freeCams.begin() + 1, freeCams.end(), [](int32_t c) { return c < 2; }), freeCams.end());
+        window_.clear();
+        for (int32_t c : freeCams) window_.push_back(imgIdxOrder[c]);
+        rcn_ba_options o;
+        rcn_ba_default_options((int32_t)freeCams.size(), &o);
+        o.fix_cam0_pose = o.fix_cam1_translation = 0;
+        rc = rcn_ba_session_solve_local(session_, freeCams.data(), (int32_t)freeCams.size(), &o, &summary, localInfo);
+        if (rc != RCN_OK && rc != RCN_ERR_NUMERIC) throw std::runtime_error(std::string("rcn_ba_session_solve_local: ") + rcn_last_error(ctx_));
+        std::vector<char> isFree((size_t)nCams, 0);
+        for (int32_t c : freeCams) isFree[c] = 1;
+        writeBack(landmarks, imgIdx2camPose, imgIdx2camIntrinsics, imgIdxOrder, isFree.data());
+        return global2local;
+    }
+
+    rcn_ba_summary summary{};
+    int32_t localInfo[4] = {0, 0, 0, 0};
+    const std::vector<int> &lastWindow() const { return window_; }
+    int rebuilds() const { return rebuilds_; }
+
+private:
+    // the containers diffed into the session: new views, every view's 12 numbers, new landmarks, the new tail of every track
+    template <class Pose4>
+    std::unordered_map<int, int> sync(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                                      std::vector<Landmark> &landmarks,
+                                      std::unordered_map<int, Pose4> &imgIdx2camPose,
+                                      std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics,
+                                      const std::vector<int> &imgIdxOrder)
     {
         const int nCams = (int)imgIdxOrder.size();
         if (!session_ || !extends(landmarks, imgIdxOrder)) reset();
@@ -104,17 +178,22 @@ public:
         }
         if (!pt.empty())
             check(rcn_ba_session_add_observations(session_, (int32_t)pt.size(), pt.data(), cam.data(), xy.data()), "rcn_ba_session_add_observations");
+        return global2local;
+    }
 
-        const int rc = rcn_ba_session_solve(session_, nullptr, &summary);       // default options: BundleAdjuster.cpp:99-142
-        if (rc != RCN_OK && rc != RCN_ERR_NUMERIC)                              // the reference ignores Ceres' summary (:145-147)
-            throw std::runtime_error(std::string("rcn_ba_session_solve: ") + rcn_last_error(ctx_));
-
-        // write back (BundleAdjuster.cpp:149-187)
+    // write back (BundleAdjuster.cpp:149-187); only: one byte per view, the views whose pose and intrinsics are written (NULL: all)
+    template <class Pose4>
+    void writeBack(std::vector<Landmark> &landmarks, std::unordered_map<int, Pose4> &imgIdx2camPose,
+                   std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics, const std::vector<int> &imgIdxOrder, const char *only)
+    {
+        const int nCams = (int)imgIdxOrder.size();
+        std::vector<double> extr(6 * (size_t)nCams), intr(6 * (size_t)nCams);
         xyz_.resize(3 * landmarks.size());
         check(rcn_ba_session_read_points(session_, xyz_.data()), "rcn_ba_session_read_points");
         for (size_t j = 0; j < landmarks.size(); ++j) { landmarks[j].x = xyz_[3 * j]; landmarks[j].y = xyz_[3 * j + 1]; landmarks[j].z = xyz_[3 * j + 2]; }
         check(rcn_ba_session_cameras(session_, extr.data(), intr.data(), nullptr, nullptr), "rcn_ba_session_cameras");
         for (int l = 0; l < nCams; ++l) {
+            if (only && !only[l]) continue;
             const int g = imgIdxOrder[l];
             Pose4 T = imgIdx2camPose[g];
             detail::angleAxisToPose(&extr[6 * l], T);
@@ -123,13 +202,8 @@ public:
             K.fX = intr[6 * l]; K.fY = intr[6 * l + 1]; K.cX = intr[6 * l + 2]; K.cY = intr[6 * l + 3];
             K.k1 = intr[6 * l + 4]; K.k2 = intr[6 * l + 5];
         }
-        return global2local;
     }
 
-    rcn_ba_summary summary{};
-    int rebuilds() const { return rebuilds_; }
-
-private:
     // the containers extend what the session holds: same view order so far, same landmarks at the same coordinates,
     // every known track a prefix of the landmark's triangulatedFeatures
     bool extends(const std::vector<Landmark> &landmarks, const std::vector<int> &imgIdxOrder) const
@@ -166,6 +240,7 @@ private:
     std::vector<std::vector<std::pair<int, int>>> tracks_;      // (imgIdx, featIdx) per landmark, in track order
     std::vector<double> xyz_;                                   // landmark coordinates as written back by the last adjust
     int rebuilds_ = 0;
+    std::vector<int> window_;                                   // image indices freed by the last adjustLocal
     rcn_ba_loss loss_{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
 };
 
