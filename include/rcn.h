@@ -51,9 +51,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * initialisation entry points and rcn_twoview_options; 7 -> 8 the optimal-matching layer rcn_sg_* and rcn_sg_options;
  * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*; 10 -> 11 the robust losses rcn_ba_solve_robust, rcn_ba_session_set_loss,
  * rcn_ba_session_loss_report; 11 -> 12 constant cameras and the local adjustment: rcn_ba_solve_constant, rcn_ba_session_solve_local,
- * rcn_ba_session_covisible, rcn_ba_session_local_seconds).
+ * rcn_ba_session_covisible, rcn_ba_session_local_seconds; 12 -> 13 the homography search rcn_homography_* and the two-view
+ * classification rcn_twoview_geometry* with their option structs).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 12
+#define RCN_ABI_REVISION 13
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -970,6 +971,62 @@ int rcn_ba_session_init_pair(rcn_ba_session *s, int32_t n, const int32_t *xy1, c
                              double min_triangulation_angle, double *E_out, double *pose34_out, uint8_t *mask_out,
                              uint8_t *cheir_mask_out, int32_t *count_out /* 2 */, int32_t *iterations_out, uint8_t *status_out,
                              int32_t *n_added_out);
+
+/* ---- homography RANSAC and two-view classification ---------------------------------------------
+ * cv::findHomography(src, dst, RANSAC, 3.0, mask, 2000, 0.995) for a batch of pairs, on the integer pixels themselves (no
+ * intrinsics): 4-entry samples from cv::RNG with the homography callback's subset check (no three points on a line in either
+ * image, equal orientation of the four triples; a rejected subset is redrawn, at most 10000 times), Hartley-normalised DLT on
+ * the four points, the forward transfer error |dst - proj(H src)|^2 in float against threshold^2, OpenCV's update of the
+ * iteration count, then a refit on the inliers of the best model (least-squares DLT, at most 10 Gauss-Newton steps on the
+ * forward transfer error) and the mask of the refitted H.  DESIGN.md section 27 writes the whole algorithm down.
+ *   pair p      entries off[p] .. off[p + 1] (int64, off[0] = 0) of xy1 (src) / xy2 (dst), in ascending query-feature order
+ *   count_out   n_pairs: inliers of the refitted H (-1: no model was accepted, -2: fewer than 4 entries; device entry: also
+ *               a pair without a resident list or without room).  Negative: every other output 0.  Exactly 4 entries: the
+ *               exact model with all four as inliers if the subset check passes, -1 otherwise.
+ *   H_out       n_pairs x 9 row-major, h33 = 1, dst ~ H src in pixels
+ *   mask_out    1 = inlier of H; iterations_out (may be NULL) sampling iterations executed
+ * RCN_ERR_ARG: a null pointer, decreasing offsets, confidence outside (0, 1), a non-positive threshold or iteration cap.
+ * opt == NULL: the defaults. */
+typedef struct { double threshold, confidence; int32_t max_iterations, reserved; } rcn_homography_options;
+void rcn_homography_default_options(rcn_homography_options *o);      /* 3.0, 0.995, 2000 */
+int rcn_homography_ransac(rcn_ctx *ctx, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
+                          const rcn_homography_options *opt, double *H_out /* n_pairs x 9 */, uint8_t *mask_out,
+                          int32_t *count_out /* n_pairs */, int32_t *iterations_out);
+/* Pairs given by image ids against the resident lists and coordinates, as rcn_twoview_init_device: the same front end, the
+ * same `capacity` rule and error codes, no host wait.  qt_dev and iterations_dev may be NULL. */
+int rcn_homography_ransac_device(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, const rcn_homography_options *opt,
+                                 int64_t capacity, int64_t *off_dev, int32_t *qt_dev, double *H_dev, uint8_t *mask_dev,
+                                 int32_t *count_dev, int32_t *iterations_dev);
+
+/* The degeneracy check of an initial pair: one call gathers the pairs' entries once and runs the E search (rcn_twoview_init,
+ * the same bits), the H search (rcn_homography_ransac, the same bits) and the classification on them.
+ *   ratio_out         count_H / count_E (0 when count_E <= 0 or count_H < 0)
+ *   median_angle_out  lower median (element (m - 1) / 2 of the ascending order) over the m entries of the cheirality mask of the
+ *                     angle between R x1 and x2 (x: the unprojected pixel, Camera.h:79-93) in the loop's own unit
+ *                     180 acos(.) / 3.1415; 0 when the mask is empty
+ *   label_out         tested in this order: RCN_TV_NO_MODEL count_E < min_inliers or m < min_inliers; RCN_TV_PANORAMIC ratio >=
+ *                     max_h_ratio and median_angle < min_angle; RCN_TV_PLANAR ratio >= max_h_ratio; RCN_TV_SMALL_BASELINE
+ *                     median_angle < min_angle; RCN_TV_GENERAL otherwise
+ * top_m is the number of candidates the callers' pair choice looks at (HipNextView.h, twoview.py); the library only checks it.
+ * Every E and H output of rcn_twoview_init / rcn_homography_ransac is required here except E_out, cheir_mask_out and the two
+ * iteration counts.  RCN_ERR_ARG: as the two searches, and max_h_ratio <= 0, top_m < 1.  NULL options: the defaults. */
+enum { RCN_TV_NO_MODEL = 0, RCN_TV_PANORAMIC = 1, RCN_TV_PLANAR = 2, RCN_TV_SMALL_BASELINE = 3, RCN_TV_GENERAL = 4 };
+typedef struct { double max_h_ratio, min_angle; int32_t min_inliers, top_m; } rcn_twoview_geometry_options;
+void rcn_twoview_geometry_default_options(rcn_twoview_geometry_options *o);      /* 0.8, 1.0, 15, 10 */
+int rcn_twoview_geometry(rcn_ctx *ctx, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
+                         const double *intr6_1, const double *intr6_2, const rcn_twoview_options *tv_opt,
+                         const rcn_homography_options *h_opt, const rcn_twoview_geometry_options *g_opt, double *E_out,
+                         double *pose34_out, uint8_t *mask_out, uint8_t *cheir_mask_out, int32_t *count_out, int32_t *iterations_out,
+                         double *H_out, uint8_t *h_mask_out, int32_t *h_count_out, int32_t *h_iterations_out, double *ratio_out,
+                         double *median_angle_out, int32_t *label_out);
+/* The same behind rcn_twoview_init_device's front end; every output pointer in DEVICE memory and required except qt_dev and
+ * the two iteration counts.  Only enqueues. */
+int rcn_twoview_geometry_device(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, const double *intr6_1_dev, const double *intr6_2_dev,
+                                const rcn_twoview_options *tv_opt, const rcn_homography_options *h_opt,
+                                const rcn_twoview_geometry_options *g_opt, int64_t capacity, int64_t *off_dev, int32_t *qt_dev,
+                                double *E_dev, double *pose34_dev, uint8_t *mask_dev, uint8_t *cheir_mask_dev, int32_t *count_dev,
+                                int32_t *iterations_dev, double *H_dev, uint8_t *h_mask_dev, int32_t *h_count_dev,
+                                int32_t *h_iterations_dev, double *ratio_dev, double *median_angle_dev, int32_t *label_dev);
 
 /* ---- epipolar filter of a pair's matches --------------------------------------------------
  * GeometricFilter::estimateFundamental (GeometricFilter.cpp:39-61) as the pair loop uses it

@@ -40,6 +40,8 @@ SYMBOLS = [
     "rcn_new_view_triangulate_device", "rcn_ba_session_grow_view",
     "rcn_pnp_default_options", "rcn_pnp_ransac", "rcn_pnp_ransac_device", "rcn_ba_session_pnp",
     "rcn_twoview_default_options", "rcn_twoview_init", "rcn_twoview_init_device", "rcn_pose34_to_pose6", "rcn_ba_session_init_pair",
+    "rcn_homography_default_options", "rcn_homography_ransac", "rcn_homography_ransac_device",
+    "rcn_twoview_geometry_default_options", "rcn_twoview_geometry", "rcn_twoview_geometry_device",
     "rcn_kp_detect_device", "rcn_kp_nms_device",
     "rcn_sg_default_options", "rcn_sg_scores_device", "rcn_sg_assign_device", "rcn_sg_match_device", "rcn_sg_set_chunk_bytes",
     "rcn_sg_net_create", "rcn_sg_net_destroy", "rcn_sg_net_set_chunk_pairs", "rcn_sg_net_forward_device", "rcn_sg_net_match_device",
@@ -111,6 +113,14 @@ class TriangulationProblem(C.Structure):
 class PnpOptions(C.Structure):
     _fields_ = [("max_projection_error", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int32),
                 ("refine_iterations", C.c_int32)]
+
+
+class HomographyOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TwoViewGeometryOptions(C.Structure):
+    _fields_ = [("max_h_ratio", C.c_double), ("min_angle", C.c_double), ("min_inliers", C.c_int32), ("top_m", C.c_int32)]
 
 
 class TwoViewOptions(C.Structure):
@@ -496,6 +506,20 @@ def load():
     L.rcn_twoview_init.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(TwoViewOptions), vp, vp, vp, vp, vp, vp]
     L.rcn_twoview_init_device.restype = C.c_int
     L.rcn_twoview_init_device.argtypes = [vp, i32, vp, vp, vp, C.POINTER(TwoViewOptions), i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rcn_homography_default_options.restype = None
+    L.rcn_homography_default_options.argtypes = [C.POINTER(HomographyOptions)]
+    L.rcn_homography_ransac.restype = C.c_int
+    L.rcn_homography_ransac.argtypes = [vp, i32, vp, vp, vp, C.POINTER(HomographyOptions), vp, vp, vp, vp]
+    L.rcn_homography_ransac_device.restype = C.c_int
+    L.rcn_homography_ransac_device.argtypes = [vp, i32, vp, C.POINTER(HomographyOptions), i64, vp, vp, vp, vp, vp, vp]
+    L.rcn_twoview_geometry_default_options.restype = None
+    L.rcn_twoview_geometry_default_options.argtypes = [C.POINTER(TwoViewGeometryOptions)]
+    L.rcn_twoview_geometry.restype = C.c_int
+    L.rcn_twoview_geometry.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(TwoViewOptions), C.POINTER(HomographyOptions),
+                                       C.POINTER(TwoViewGeometryOptions)] + [vp] * 13
+    L.rcn_twoview_geometry_device.restype = C.c_int
+    L.rcn_twoview_geometry_device.argtypes = [vp, i32, vp, vp, vp, C.POINTER(TwoViewOptions), C.POINTER(HomographyOptions),
+                                              C.POINTER(TwoViewGeometryOptions), i64] + [vp] * 15
     L.rcn_pose34_to_pose6.restype = C.c_int
     L.rcn_pose34_to_pose6.argtypes = [vp, vp]
     L.rcn_ba_session_init_pair.restype = C.c_int

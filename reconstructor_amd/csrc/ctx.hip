@@ -8,9 +8,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.12 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.13 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.12 (gfx950)";
+    return "reconstructor_amd 0.13 (gfx950)";
 #endif
 }
 
@@ -111,6 +111,7 @@ void rcn_destroy(rcn_ctx *ctx)
     if (ctx->img_ev) (void)hipEventDestroy(ctx->img_ev);
     ctx->pnp_hws.release(); ctx->pnp_slots.release();
     ctx->tv_hws.release(); ctx->tv_dws.release(); ctx->tv_fws.release();
+    ctx->hg_hws.release(); ctx->hg_dws.release();
     if (ctx->tv_ev) (void)hipEventDestroy(ctx->tv_ev);
     if (ctx->pnp_ev) (void)hipEventDestroy(ctx->pnp_ev);
     if (ctx->ev_made) {

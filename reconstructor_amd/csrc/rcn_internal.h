@@ -271,7 +271,8 @@ struct rcn_ctx {
     hipEvent_t pnp_ev = nullptr;
     bool pnp_slots_pending = false;
     DevBuf tv_hws, tv_dws, tv_fws;      // two-view initialisation (twoview.hip): host-API staging and workspace, workspace of the device entry, of its fill (corr2d3d.hip)
-    std::vector<char> tv_stage_host;    // staging of the device entry's pair table (uploaded asynchronously; tv_ev marks the copy)
+    DevBuf hg_hws, hg_dws;              // homography search and two-view geometry (homography.hip): host-API staging and workspace, workspace of the device entries
+    std::vector<char> tv_stage_host;   // staging of the device entry's pair table (uploaded asynchronously; tv_ev marks the copy)
     hipEvent_t tv_ev = nullptr;
     bool tv_stage_pending = false;
     int64_t corr_budget = 1ll << 30;    // bytes of hit rows per batch (rcn_corr_set_workspace_bytes)
@@ -361,6 +362,11 @@ int rcn_int_pnp_host(rcn_ctx *ctx, const char *who, int32_t n_views, const int64
 int rcn_int_twoview_host(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
                          const double *intr6_1, const double *intr6_2, const rcn_twoview_options *opt, double *E_out,
                          double *pose34_out, uint8_t *mask_out, uint8_t *cheir_mask_out, int32_t *count_out, int32_t *iterations_out);
+// twoview.hip: k_tv_pair on entries in device memory with ctx->mu held (rcn_twoview_geometry, homography.hip); n_pairs == 0 only checks opt
+int rcn_int_twoview_launch(rcn_ctx *ctx, const char *who, const rcn_twoview_options *opt, int32_t n_pairs, const int64_t *off_dev,
+                           const int32_t *xy1_dev, const int32_t *xy2_dev, const double *intr6_1_dev, const double *intr6_2_dev,
+                           double *norm_dev, double *E_dev, double *pose34_dev, uint8_t *mask_dev, uint8_t *cheir_mask_dev,
+                           int32_t *count_dev, int32_t *iterations_dev);
 // corr2d3d.hip, with ctx->mu held: the entries of directed pairs from the resident lists, ascending query order (rcn_twoview_init_device)
 int rcn_int_pair_fill(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int32_t *pairs, int64_t capacity, int64_t *off_dev,
                       int32_t *xy1_dev, int32_t *xy2_dev, int32_t *qt_dev);

@@ -800,6 +800,22 @@ int launch(rcn_ctx *ctx, const TvArgs &a, int32_t n_pairs)
 
 }  // namespace
 
+// k_tv_pair on entries that already lie in device memory, with ctx->mu held (rcn_twoview_geometry, homography.hip): the
+// options checked as rcn_twoview_init checks them; n_pairs == 0 checks them only.
+int rcn_int_twoview_launch(rcn_ctx *ctx, const char *who, const rcn_twoview_options *opt, int32_t n_pairs, const int64_t *off_dev,
+                           const int32_t *xy1_dev, const int32_t *xy2_dev, const double *intr6_1_dev, const double *intr6_2_dev,
+                           double *norm_dev, double *E_dev, double *pose34_dev, uint8_t *mask_dev, uint8_t *cheir_mask_dev,
+                           int32_t *count_dev, int32_t *iterations_dev)
+{
+    int rc = check_options(ctx, who, opt);
+    if (rc || n_pairs == 0) return rc;
+    TvArgs a{};
+    a.off = off_dev; a.xy1 = xy1_dev; a.xy2 = xy2_dev; a.intr1 = intr6_1_dev; a.intr2 = intr6_2_dev; a.norm = norm_dev;
+    a.E = E_dev; a.pose = pose34_dev; a.mask = mask_dev; a.cmask = cheir_mask_dev; a.count = count_dev; a.iters = iterations_dev;
+    fill_args(a, opt);
+    return launch(ctx, a, n_pairs);
+}
+
 // rcn_twoview_init with ctx->mu held (rcn_ba_session_init_pair)
 int rcn_int_twoview_host(rcn_ctx *ctx, const char *who, int32_t n_pairs, const int64_t *off, const int32_t *xy1, const int32_t *xy2,
                          const double *intr6_1, const double *intr6_2, const rcn_twoview_options *opt, double *E_out,

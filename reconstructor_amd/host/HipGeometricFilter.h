@@ -83,6 +83,30 @@ public:
         for (size_t i = 0; i < n; ++i) inlierMatchIds.push_back(mask[i] != 0);
         return E;
     }
+    // cv::findHomography(pts1, pts2, cv::RANSAC, 3.0, mask, 2000, 0.995) through rcn_homography_ransac, beside the two above:
+    // inlierMatchIds is appended to, one flag per match, exactly when a model was found; a zero matrix otherwise.
+    // lastInliers() is the number of inliers of the returned H (-1 / -2: none).
+    Mat3d estimateHomography(const std::vector<FeaturePtr<>> &features1, const std::vector<FeaturePtr<>> &features2,
+                             std::vector<bool> &inlierMatchIds)
+    {
+        const size_t n = features1.size();
+        if (features2.size() != n) throw std::invalid_argument("estimateHomography: one feature of image 2 per feature of image 1");
+        std::vector<int32_t> xy1(2 * n + 2), xy2(2 * n + 2);
+        for (size_t i = 0; i < n; ++i) {      // featuresToCvPoints, utils.cpp:165-177
+            xy1[2 * i] = features1[i]->featCoord.x; xy1[2 * i + 1] = features1[i]->featCoord.y;
+            xy2[2 * i] = features2[i]->featCoord.x; xy2[2 * i + 1] = features2[i]->featCoord.y;
+        }
+        const int64_t off[2] = {0, (int64_t)n};
+        std::vector<uint8_t> mask(n + 1);
+        Mat3d H;
+        lastCount_[0] = lastCount_[1] = 0;
+        for (double &p : lastPose_) p = 0.0;
+        if (rcn_homography_ransac(ctx_, 1, off, xy1.data(), xy2.data(), nullptr, H.m, mask.data(), lastCount_, nullptr) != RCN_OK)
+            throw std::runtime_error(std::string("estimateHomography: ") + rcn_last_error(ctx_));
+        if (lastCount_[0] < 0) return Mat3d();
+        for (size_t i = 0; i < n; ++i) inlierMatchIds.push_back(mask[i] != 0);
+        return H;
+    }
     // of the last estimateEssential: rows of [R | t] of the second camera (zeros when there was no model), the number of
     // inliers (-1 / -2: none) and of inliers in front of both cameras
     const double *lastPose34() const { return lastPose_; }

@@ -179,6 +179,97 @@ public:
         return T;
     }
 
+    // One candidate of chooseInitialPairByGeometry: the pair, its number of matches and what rcn_twoview_geometry says of it.
+    struct PairGeometry {
+        int imgIdx1 = 0, imgIdx2 = 0, matches = 0;
+        int inliersE = 0, inFront = 0, inliersH = 0, label = RCN_TV_NO_MODEL;
+        double ratio = 0.0, medianAngle = 0.0;
+    };
+    struct PairChoiceReport {
+        std::vector<PairGeometry> candidates;   // in candidate order
+        int chosen = 0;                         // index into candidates
+        bool fallback = false;                  // no candidate passed: candidate 0, the reference's choice
+    };
+
+    // chooseInitialPair with a degeneracy check.  The candidates are the options.top_m pairs with the
+    // most matches, in chooseInitialPair's order (size descending, then (i, j)); one rcn_twoview_geometry call runs the E
+    // search, the H search and the classification on all of them; the choice is the first RCN_TV_GENERAL candidate, else the
+    // first RCN_TV_PLANAR one, else candidate 0 with report->fallback set -- exactly chooseInitialPair's pair.  Returns the pose
+    // of the chosen pair as chooseInitialPair does (the same bits for the same pair); throws when there are no matches or
+    // the chosen pair has no model.  options == NULL: the defaults.
+    template <class Pose4 = Mat4d, class FeatureMatches>
+    Pose4 chooseInitialPairByGeometry(int &imgIdx1, int &imgIdx2, std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
+                                      const FeatureMatches &featureMatches, std::unordered_map<int, PinholeCamera> &imgIdx2camIntrinsics,
+                                      const rcn_twoview_geometry_options *options = nullptr, std::vector<bool> *inlierMatchIds = nullptr,
+                                      PairChoiceReport *report = nullptr)
+    {
+        rcn_twoview_geometry_options o;
+        if (options) o = *options; else rcn_twoview_geometry_default_options(&o);
+        if (o.top_m < 1) throw std::runtime_error("chooseInitialPairByGeometry: top_m >= 1");
+        std::vector<std::pair<std::pair<long, std::pair<int, int>>, const typename FeatureMatches::mapped_type *>> order;
+        for (const auto &[key, m] : featureMatches)
+            order.push_back({{-(long)m.size(), {key.first, key.second}}, &m});
+        if (order.empty()) throw std::runtime_error("chooseInitialPairByGeometry: no matches");
+        std::sort(order.begin(), order.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+        if (order.size() > (size_t)o.top_m) order.resize((size_t)o.top_m);
+        const size_t nc = order.size();
+        std::vector<int64_t> off(nc + 1, 0);
+        std::vector<int32_t> xy1, xy2;
+        std::vector<double> K1, K2;
+        for (size_t c = 0; c < nc; ++c) {
+            const int a = order[c].first.second.first, b = order[c].first.second.second;
+            std::vector<std::pair<int, int>> qt(order[c].second->begin(), order[c].second->end());
+            std::sort(qt.begin(), qt.end());
+            for (const auto &e : qt) {
+                const auto &pa = features.at(a).at(e.first)->featCoord, &pb = features.at(b).at(e.second)->featCoord;
+                xy1.push_back(pa.x); xy1.push_back(pa.y); xy2.push_back(pb.x); xy2.push_back(pb.y);
+            }
+            off[c + 1] = off[c] + (int64_t)qt.size();
+            const PinholeCamera &k1 = imgIdx2camIntrinsics.at(a), &k2 = imgIdx2camIntrinsics.at(b);
+            for (double v : {k1.fX, k1.fY, k1.cX, k1.cY, k1.k1, k1.k2}) K1.push_back(v);
+            for (double v : {k2.fX, k2.fY, k2.cX, k2.cY, k2.k1, k2.k2}) K2.push_back(v);
+        }
+        const size_t ne = (size_t)off[nc];
+        xy1.resize(2 * ne + 2); xy2.resize(2 * ne + 2);
+        std::vector<double> P(12 * nc), H(9 * nc), ratio(nc), angle(nc);
+        std::vector<uint8_t> mask(ne + 1), hmask(ne + 1);
+        std::vector<int32_t> count(2 * nc), hcount(nc), label(nc);
+        check(rcn_twoview_geometry(ctx_, (int32_t)nc, off.data(), xy1.data(), xy2.data(), K1.data(), K2.data(), nullptr, nullptr, &o, nullptr,
+                                   P.data(), mask.data(), nullptr, count.data(), nullptr, H.data(), hmask.data(), hcount.data(), nullptr,
+                                   ratio.data(), angle.data(), label.data()),
+              "rcn_twoview_geometry");
+        size_t pick = 0;
+        bool fallback = true;
+        for (int want : {(int)RCN_TV_GENERAL, (int)RCN_TV_PLANAR}) {
+            for (size_t c = 0; c < nc && fallback; ++c)
+                if (label[c] == want) { pick = c; fallback = false; }
+            if (!fallback) break;
+        }
+        if (report) {
+            report->candidates.clear();
+            for (size_t c = 0; c < nc; ++c) {
+                PairGeometry g;
+                g.imgIdx1 = order[c].first.second.first; g.imgIdx2 = order[c].first.second.second; g.matches = (int)(off[c + 1] - off[c]);
+                g.inliersE = count[2 * c]; g.inFront = count[2 * c + 1]; g.inliersH = hcount[c]; g.label = label[c];
+                g.ratio = ratio[c]; g.medianAngle = angle[c];
+                report->candidates.push_back(g);
+            }
+            report->chosen = (int)pick; report->fallback = fallback;
+        }
+        imgIdx1 = order[pick].first.second.first; imgIdx2 = order[pick].first.second.second;
+        if (count[2 * pick] < 0)
+            throw std::runtime_error("chooseInitialPairByGeometry: no pose for the pair (" + std::to_string(imgIdx1) + ", " + std::to_string(imgIdx2) +
+                                     (count[2 * pick] == -2 ? ") (fewer than 5 matches)" : ") (no model)"));
+        if (inlierMatchIds) {
+            inlierMatchIds->clear();
+            for (int64_t e = off[pick]; e < off[pick + 1]; ++e) inlierMatchIds->push_back(mask[(size_t)e] != 0);
+        }
+        Pose4 T;
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T(r, c) = r == c ? 1.0 : 0.0;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T(r, c) = P[12 * pick + 4 * r + c];
+        return T;
+    }
+
     // :559-638.  maxProjectionError is the threshold (:596), confidence 0.99 and 10000 iterations as the reference passes them.
     template <class Pose4 = Mat4d>
     Pose4 registerImagePnP(int imgIdx, std::vector<int> &featureIdxs, std::vector<int> &landmarkIdxs,
