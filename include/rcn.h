@@ -52,9 +52,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * 8 -> 9 the graph network rcn_sg_net_*; 9 -> 10 SuperPoint's convolutional network rcn_sp_net_*; 10 -> 11 the robust losses rcn_ba_solve_robust, rcn_ba_session_set_loss,
  * rcn_ba_session_loss_report; 11 -> 12 constant cameras and the local adjustment: rcn_ba_solve_constant, rcn_ba_session_solve_local,
  * rcn_ba_session_covisible, rcn_ba_session_local_seconds; 12 -> 13 the homography search rcn_homography_* and the two-view
- * classification rcn_twoview_geometry* with their option structs).
+ * classification rcn_twoview_geometry* with their option structs; 13 -> 14 shared intrinsics: rcn_ba_solve_tied,
+ * rcn_ba_session_set_groups).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 13
+#define RCN_ABI_REVISION 14
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -596,6 +597,29 @@ int rcn_ba_solve_robust(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_b
 int rcn_ba_solve_constant(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options, const rcn_ba_loss *loss,
                           const uint8_t *cam_constant, rcn_ba_summary *summary, rcn_ba_loss_report *report, double *weights_host);
 
+/* Shared intrinsics: cameras tied in groups.  cam_group: n_cams int32; -1 = the camera's own intrinsics; equal values >= 0 = one
+ * physical camera, whose fx, fy, k1, k2 are ONE set of four unknowns in intrinsics_mode 1 (cx, cy stay constant, as for every camera).
+ * What is solved is the problem with one parameter block per group: the reduced system of the per-camera problem, S delta = b, is
+ * folded to S' = P' S P, b' = P' b (P: one 1 per row, the members' columns onto their group's), factorised, and the step expanded
+ * again, delta = P delta'.
+ *   No groups.  cam_group == NULL, all -1, intrinsics_mode 0, or nothing but groups of one camera: rcn_ba_solve_constant, bit for bit,
+ *     with the same kernels and launches (a group of one camera is its own camera).
+ *   Members must agree on entry: the members of a group enter with bit-identical intr6, all six numbers; otherwise RCN_ERR_ARG, the
+ *     message names the first offending camera.  They leave bit-identical.
+ *   Constant members.  A group with a constant member (cam_constant) has its intrinsics held for every member: its free members keep
+ *     their pose columns and have no intrinsics columns (a free camera then has 6, 3 or 0 columns in mode 1).
+ *   Column order of the tied system: cameras in index order, each with its pose columns and, when it is in no group, its own four
+ *     intrinsics columns; then the groups in ascending order of their smallest member, four columns each (fx, fy, k1, k2).
+ *   rcn_ba_summary::reduced_dim is the tied system's size.  The focal bound, and the projection onto it at entry, apply to a tied
+ *     column once: bound_projections counts a tied focal length once, not once per member.
+ *   Jacobi scale of a tied column: 1 / (1 + sqrt(sum over the members of the raw diagonal)).  LM diagonal: clamp(scale^2 * that sum,
+ *     min_lm_diagonal, max_lm_diagonal) / radius -- the clamp of the sum.  The step norm, |x|, gradient . step and the gradient's
+ *     max-norm (the members' gradients summed) count a tied parameter once.  No float atomics: a tied solve is bit-reproducible.
+ * RCN_ERR_ARG with a message (nothing written): a group id below -1, members that disagree. */
+int rcn_ba_solve_tied(rcn_ctx *ctx, const rcn_ba_problem *problem, const rcn_ba_options *options, const rcn_ba_loss *loss,
+                      const uint8_t *cam_constant, const int32_t *cam_group, rcn_ba_summary *summary, rcn_ba_loss_report *report,
+                      double *weights_host);
+
 /* Introspection, pure host code (no device, no ctx): the SCHEDULE of the dense factorisation inside rcn_ba_solve for a reduced system of
  * n_blocks 128-row blocks (csrc/chol_plan.h) -- the list of tile operations in an order that is a correct sequential algorithm, each
  * with its stream and the device counters it waits for, and the tile maps of the pipelined launches.  tests/test_chol_plan.py executes
@@ -667,6 +691,11 @@ int  rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss);
 /* rcn_ba_solve_robust's report and weights at the session's current state (its cameras, points and graph as they stand), under
  * the session's loss; either pointer may be NULL, weights_host holds n_obs doubles. */
 int  rcn_ba_session_loss_report(rcn_ba_session *s, rcn_ba_loss_report *report, double *weights_host);
+/* The groups of every later rcn_ba_session_solve (rcn_ba_solve_tied's arithmetic on the same problem, bit for bit) and
+ * rcn_ba_session_solve_local (the groups mapped through the window's camera map; a group with a member among the window's constant
+ * cameras is held).  Kept across solves; cameras added later are -1 until set again.  n must equal the camera count, an id below -1 is
+ * refused (RCN_ERR_ARG with a message, the session's groups unchanged); cam_group == NULL with n == 0 clears them. */
+int  rcn_ba_session_set_groups(rcn_ba_session *s, const int32_t *cam_group, int32_t n);
 int  rcn_ba_session_read_points(rcn_ba_session *s, double *xyz_host);
 const double *rcn_ba_session_points_device(rcn_ba_session *s);      /* n_points x 3 in HBM; valid until the next add / remove */
 /* checkLandmarkValidity (SequentialReconstructor.cpp:869-954) on the session's arrays, on the device.  poses34_host:

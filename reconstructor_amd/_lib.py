@@ -19,7 +19,7 @@ SYMBOLS = [
     "rcn_create", "rcn_destroy", "rcn_last_error", "rcn_version", "rcn_set_stream",
     "rcn_synchronize", "rcn_desc_upload", "rcn_desc_upload_device", "rcn_desc_upload_batch_device", "rcn_desc_upload_batch", "rcn_desc_remove", "rcn_desc_sample_device", "rcn_desc_sample_errors", "rcn_desc_sample_batch_device", "rcn_desc_clear",
     "rcn_desc_count", "rcn_match_pair", "rcn_match_grid", "rcn_match_grid_device",
-    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_solve_robust", "rcn_ba_solve_constant", "rcn_ba_factor_plan",
+    "rcn_match_last_stats", "rcn_match_profile", "rcn_match_set_workspace_rows", "rcn_ba_default_options", "rcn_ba_solve", "rcn_ba_solve_robust", "rcn_ba_solve_constant", "rcn_ba_solve_tied", "rcn_ba_factor_plan",
     "rcn_landmark_validity", "rcn_landmark_validity_device",
     "rcn_fmat_filter", "rcn_fmat_filter_grid", "rcn_fmat_filter_grid_device",
     "rcn_coords_upload", "rcn_coords_upload_batch", "rcn_coords_clear", "rcn_match_table_filter_device",
@@ -30,7 +30,7 @@ SYMBOLS = [
     "rcn_shard_fail", "rcn_shard_set_timeout", "rcn_shard_gather_lists", "rcn_shard_merge_lists", "rcn_shard_profile", "rcn_shard_profile_read", "rcn_shard_filter", "rcn_match_grid_filtered",
     "rcn_ba_session_create", "rcn_ba_session_destroy", "rcn_ba_session_add_camera", "rcn_ba_session_cameras",
     "rcn_ba_session_add_points", "rcn_ba_session_add_observations", "rcn_ba_session_counts", "rcn_ba_session_graph",
-    "rcn_ba_session_solve", "rcn_ba_session_set_loss", "rcn_ba_session_loss_report", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
+    "rcn_ba_session_solve", "rcn_ba_session_set_loss", "rcn_ba_session_set_groups", "rcn_ba_session_loss_report", "rcn_ba_session_read_points", "rcn_ba_session_points_device", "rcn_ba_session_validity",
     "rcn_ba_session_remove_outliers", "rcn_ba_session_triangulate",
     "rcn_ba_session_solve_local", "rcn_ba_session_covisible", "rcn_ba_session_local_seconds",
     "rcn_triangulate", "rcn_triangulate_device",
@@ -446,6 +446,10 @@ def load():
     L.rcn_ba_session_graph.argtypes = [vp, vp, vp, vp]
     L.rcn_ba_session_solve.restype = C.c_int
     L.rcn_ba_session_solve.argtypes = [vp, C.POINTER(BaOptions), C.POINTER(BaSummary)]
+    L.rcn_ba_solve_tied.restype = C.c_int
+    L.rcn_ba_solve_tied.argtypes = [vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaLoss), vp, vp, C.POINTER(BaSummary), C.POINTER(BaLossReport), vp]
+    L.rcn_ba_session_set_groups.restype = C.c_int
+    L.rcn_ba_session_set_groups.argtypes = [vp, vp, i32]
     L.rcn_ba_session_set_loss.restype = C.c_int
     L.rcn_ba_session_set_loss.argtypes = [vp, C.POINTER(BaLoss)]
     L.rcn_ba_session_loss_report.restype = C.c_int

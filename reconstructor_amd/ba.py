@@ -46,8 +46,10 @@ def loss_report_dict(r):
 
 
 def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=None, allow_failure=False, loss=None, report=False,
-               constant=None):
+               constant=None, groups=None):
     """Returns (poses, intrinsics, points, summary); inputs are copied, not modified.
+    groups: None or one int per camera (rcn_ba_solve_tied): -1 = the camera's own intrinsics, equal values >= 0 = one physical camera,
+    whose fx, fy, k1, k2 are one set of unknowns in intrinsics mode 1; members enter and leave with bit-identical intrinsics.
     constant: None or a mask over the cameras (rcn_ba_solve_constant): a camera with a true entry has no free parameter and comes
     back unchanged bit for bit.
     allow_failure: a solve that ends in RCN_BA_FAILURE (RCN_ERR_NUMERIC; the summary is filled) returns instead of raising.
@@ -66,10 +68,22 @@ def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=
                         pt.ctypes.data if pt.size else None)
     o = options if options is not None else default_options(ctx, poses.shape[0])
     s = _lib.BaSummary()
+    mask = None
     if constant is not None:
         mask = np.ascontiguousarray(np.asarray(constant) != 0, np.uint8)
         if mask.shape != (poses.shape[0],):
             raise ValueError("solve_flat: constant must hold one entry per camera")
+    if groups is not None:
+        grp = np.ascontiguousarray(groups, np.int32)
+        if grp.shape != (poses.shape[0],):
+            raise ValueError("solve_flat: groups must hold one entry per camera")
+        ls = make_loss(loss)
+        rep = _lib.BaLossReport()
+        w = np.zeros(max(cam.shape[0], 1))
+        rc = ctx.lib.rcn_ba_solve_tied(ctx.h, C.byref(pb), C.byref(o), C.byref(ls) if ls is not None else None,
+                                       mask.ctypes.data if mask is not None else None, grp.ctypes.data,
+                                       C.byref(s), C.byref(rep) if report else None, w.ctypes.data if report else None)
+    elif constant is not None:
         ls = make_loss(loss)
         rep = _lib.BaLossReport()
         w = np.zeros(max(cam.shape[0], 1))
@@ -91,9 +105,9 @@ def solve_flat(ctx, poses, intrinsics, points, obs_uv, obs_cam, obs_pt, options=
     return poses, intr, pts, d
 
 
-def solve_scene(ctx, scene, options=None, allow_failure=False, loss=None, report=False, constant=None):
+def solve_scene(ctx, scene, options=None, allow_failure=False, loss=None, report=False, constant=None, groups=None):
     return solve_flat(ctx, scene["poses"], scene["intrinsics"], scene["points"], scene["obs_uv"],
-                      scene["obs_cam"], scene["obs_pt"], options, allow_failure, loss, report, constant)
+                      scene["obs_cam"], scene["obs_pt"], options, allow_failure, loss, report, constant, groups)
 
 
 def _rot_to_angle_axis(R):
@@ -271,6 +285,15 @@ class BaSession:
         """the loss of every later solve (rcn_ba_session_set_loss): None switches it off"""
         ls = make_loss(loss)
         self.ctx.check(self.ctx.lib.rcn_ba_session_set_loss(self.h, C.byref(ls) if ls is not None else None))
+
+    def set_groups(self, groups):
+        """the groups of every later solve and solve_local (rcn_ba_session_set_groups): one int per camera, -1 = its own intrinsics;
+        None clears them.  Cameras added afterwards are -1 until set again."""
+        if groups is None:
+            self.ctx.check(self.ctx.lib.rcn_ba_session_set_groups(self.h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, np.int32).reshape(-1)
+        self.ctx.check(self.ctx.lib.rcn_ba_session_set_groups(self.h, g.ctypes.data if len(g) else None, len(g)))
 
     def loss_report(self):
         """(rcn_ba_loss_report as a dict, rho'(s) per observation) at the session's current state, under its loss"""

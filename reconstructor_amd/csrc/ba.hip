@@ -24,6 +24,7 @@
 #include <utility>
 #include "ba_linesearch.h"
 #include "ba_loss.h"
+#include "ba_tied.h"
 
 #include <cfloat>
 #include <chrono>
@@ -364,7 +365,9 @@ __global__ __launch_bounds__(JAC ? 128 : 256) void k_ba_eval(BaDev d, const doub
             // tangent columns of this camera, WITHOUT indexing J by a run-time column (that would put J in scratch
             // memory): the host lays them out as the first `npose` pose columns (0, 3 or 6: camera 0 / camera 1 / the
             // others, BundleAdjuster.cpp:100-105) followed, in intrinsics mode 1, by fx fy k1 k2 = columns 6 7 10 11
-            const int dc = d.cam_dim[c], nin = d.mode == 1 ? 4 : 0, npose = dc - nin;
+            // (a camera whose group's intrinsics are held, ba_tied.h, has pose columns only in mode 1 too: 6, 3 or 0 columns where a
+            //  camera with intrinsics columns has 10, 7 or 4 -- the two sets are apart, so the count says which)
+            const int dc = d.cam_dim[c], nin = (d.mode == 1 && dc % 3 == 1) ? 4 : 0, npose = dc - nin;
             double row[JROW];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -1470,6 +1473,17 @@ int rcn_ba_solve_constant(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_o
     return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr, loss, report, weights_host, cam_constant);
 }
 
+int rcn_ba_solve_tied(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, const rcn_ba_loss *loss, const uint8_t *cam_constant,
+                      const int32_t *cam_group, rcn_ba_summary *sum, rcn_ba_loss_report *report, double *weights_host)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (pb && cam_group)
+        for (int32_t c = 0; c < pb->n_cams; ++c)      // (below -1: the library's own mark for a held camera, not a caller's)
+            if (cam_group[c] < -1) { ctx->set_error("rcn_ba_solve_tied: camera " + std::to_string(c) + ": group id " + std::to_string(cam_group[c]) + " is below -1"); return RCN_ERR_ARG; }
+    return rcn_int_ba_solve(ctx, pb, opt, sum, nullptr, loss, report, weights_host, cam_constant, cam_group);
+}
+
 }  // extern "C"
 
 // The loss as the kernels take it.  NULL: no loss, and a report counts nothing beyond the scale (b = inf).
@@ -1528,8 +1542,10 @@ int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const 
 // cam_constant != nullptr (n_cams bytes): a camera with a non-zero byte has no tangent column at all (cam_dim = 0, in intrinsics mode 1
 // too) -- its observations are residuals of the landmarks alone, its 12 numbers come back as they went in.  The kernels read the
 // tables, so nothing but the tables (and the three places marked "constant camera" below) knows of it.
+// cam_group != nullptr (n_cams words): cameras that share one set of intrinsics (ba_tied.h, ba_tied.hip).  The
+// Schur build still makes the per-camera system; the factorisation reads its fold, and the step is expanded again behind it.
 int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
-                     const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host, const uint8_t *cam_constant)
+                     const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host, const uint8_t *cam_constant, const int32_t *cam_group)
 {
     if (!pb || !opt || !sum || pb->n_cams <= 0 || pb->n_points < 0 || pb->n_obs < 0 || !pb->poses ||
         !pb->intrinsics || (pb->n_points > 0 && !pb->points && !res) ||
@@ -1540,8 +1556,17 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     BaLoss ls;
     { const int rcl = rcn_int_ba_loss_check(ctx, loss, "rcn_ba_solve_robust", &ls.kind, &ls.a, &ls.b); if (rcl) return rcl; }
     const bool robust = ls.kind != RCN_BA_LOSS_TRIVIAL;
-    memset(sum, 0, sizeof(*sum));
     const int nc = pb->n_cams, np = pb->n_points, no = pb->n_obs;
+    // shared intrinsics (ba_tied.h): `tied` is false without a live group or a held camera, and the solve is then
+    // the one without groups -- the same tables, the same launches.  Everything tied below sits behind that flag.
+    ba_tied::Plan tp;
+    if (cam_group && ba_tied::build(nc, opt->intrinsics_mode, opt->fix_cam0_pose != 0, opt->fix_cam1_translation != 0, cam_constant, cam_group, nc,
+                                    pb->intrinsics, tp, true)) {
+        ctx->set_error("rcn_ba_solve_tied: " + tp.error);
+        return RCN_ERR_ARG;
+    }
+    const bool tied = tp.tied;
+    memset(sum, 0, sizeof(*sum));
     RCN_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
@@ -1576,9 +1601,12 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         cam_off[c] = n; cam_dim[c] = dcm; n += dcm;
     }
     cam_off[nc] = n;
+    if (tied) { cam_off = tp.cam_off; cam_dim = tp.cam_dim; cols = tp.cols; n = tp.n; }      // (a held camera has lost its intrinsics columns)
     if (n == 0) { ctx->set_error("rcn_ba_solve: the reduced system has no free parameter (every camera is constant)"); return RCN_ERR_ARG; }
-    const int npad = std::max(chol::BLOCK, (n + chol::BLOCK - 1) / chol::BLOCK * chol::BLOCK), nblk = npad / chol::BLOCK;
-    sum->reduced_dim = n;
+    const int npad = std::max(chol::BLOCK, (n + chol::BLOCK - 1) / chol::BLOCK * chol::BLOCK);
+    // the system the factorisation reads: the per-camera one, or (tied) its fold
+    const int n_f = tied ? tp.n_tied : n, npad_f = std::max(chol::BLOCK, (n_f + chol::BLOCK - 1) / chol::BLOCK * chol::BLOCK), nblk_f = npad_f / chol::BLOCK;
+    sum->reduced_dim = n_f;
 
     // ---- device workspace
     Ws ws{ctx};
@@ -1606,7 +1634,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     d.Vinv = ws.get<double>(9 * (size_t)np);
     d.S = ws.get<double>((size_t)npad * npad);
     d.L = ws.get<double>((size_t)npad * npad);
-    const CholWs cws = rcn_chol_ws(ctx, nblk);
+    const CholWs cws = rcn_chol_ws(ctx, nblk_f);
     d.Linv = ws.get<double>(cws.linv);
     double *SI = ws.get<double>(cws.si);      // a super-block's inverse (two-level regime of the factorisation)
     double *Sb = ws.get<double>(100 * (size_t)nc * nc);
@@ -1631,6 +1659,17 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     const int eb = (no + 255) / 256, ebj = (no + 127) / 128, pbk = (std::max(nc, np) + 255) / 256;
     d.partial = ws.get<double>(4 * (size_t)std::max(std::max(ebj, pbk), 1) + 16);
     d.scal = ws.get<double>(32);
+    ba_tied::Dev T;
+    memset(&T, 0, sizeof(T));
+    double *yc2 = nullptr;
+    int *tints = nullptr;
+    const size_t tints_n = (size_t)nc + 2 * (size_t)n + (size_t)n_f + 1 + tp.grp_off.size() + tp.grp_cam.size();
+    if (tied) {
+        T.S2 = ws.get<double>((size_t)npad_f * npad_f);
+        double *tv = ws.get<double>(4 * (size_t)n * tp.n_groups + 4 * (size_t)tp.n_groups + 2 * (size_t)npad_f + 16);
+        T.C = tv; T.dgt = tv + 4 * (size_t)n * tp.n_groups; T.rhs2 = T.dgt + 4 * (size_t)tp.n_groups; yc2 = T.rhs2 + npad_f;
+        tints = ws.get<int>(tints_n);
+    }
     if (ws.err != hipSuccess) { ctx->set_error(std::string("rcn_ba_solve: workspace: ") + hipGetErrorString(ws.err)); return RCN_ERR_HIP; }
     d.uv = uv; d.ocam = p_ocam; d.opt = p_opt; d.cam_obs = p_camobs; d.pt_off = p_ptoff; d.cam_obs_off = p_camobsoff;
     d.cam_off = p_camoff; d.cam_dim = p_camdim; d.cols = p_cols; d.flag = p_flag;
@@ -1642,7 +1681,10 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     if (opt->intrinsics_mode == 1)
         for (int c = 0; c < nc; ++c)
             for (int k = 0; k < 2; ++k)      // (cam_dim == 0 in mode 1: a constant camera, not part of the box)
-                if (cam_dim[c] > 0 && intr0[6 * c + k] > opt->focal_upper_bound) { intr0[6 * c + k] = opt->focal_upper_bound; sum->bound_projections++; }
+                if ((tied ? tp.intr_free[c] != 0 : cam_dim[c] > 0) && intr0[6 * c + k] > opt->focal_upper_bound) {
+                    intr0[6 * c + k] = opt->focal_upper_bound;
+                    if (!tied || tp.grp[c] < 0 || tp.grp_cam[tp.grp_off[tp.grp[c]]] == c) sum->bound_projections++;      // (a tied focal length counts once)
+                }
     RCN_HIP(H2D(d.intr, intr0.data(), sizeof(double) * 6 * nc));
     if (res) {
         if (np > 0) RCN_HIP(hipMemcpyAsync(d.pts, res->pts, sizeof(double) * 3 * np, hipMemcpyDeviceToDevice, st));
@@ -1660,6 +1702,18 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         auto put = [&](const std::vector<int> &v, size_t cnt) { if (cnt) memcpy(o, v.data(), cnt * sizeof(int)); o += cnt; };
         put(cam_obs, (size_t)no); put(pt_off, (size_t)np + 1); put(cam_obs_off, (size_t)nc + 1); put(cam_off, (size_t)nc + 1); put(cam_dim, (size_t)nc); put(cols, 10 * (size_t)nc);
         RCN_HIP(H2D(p_camobs, stage.data(), stage.size() * sizeof(int)));
+        if (tied) {      // the tied tables, back to back: grp, map, src_off, src, grp_off, grp_cam
+            std::vector<int> ts;
+            ts.reserve(tints_n);
+            for (const std::vector<int> *v : {&tp.grp, &tp.map, &tp.src_off, &tp.src, &tp.grp_off, &tp.grp_cam}) ts.insert(ts.end(), v->begin(), v->end());
+            RCN_HIP(H2D(tints, ts.data(), ts.size() * sizeof(int)));
+            T.nc = nc; T.n = n; T.npad = npad; T.n_tied = n_f; T.npad_tied = npad_f; T.n_own = tp.n_own; T.n_groups = tp.n_groups;
+            T.mode = opt->intrinsics_mode; T.ub = opt->focal_upper_bound;
+            T.cam_off = p_camoff; T.cam_dim = p_camdim; T.cols = p_cols; T.cam_obs_off = p_camobsoff;
+            T.grp = tints; T.map = T.grp + nc; T.src_off = T.map + n; T.src = T.src_off + n_f + 1; T.grp_off = T.src + n; T.grp_cam = T.grp_off + tp.grp_off.size();
+            RCN_HIP(hipMemsetAsync(T.S2, 0, sizeof(double) * (size_t)npad_f * npad_f, st));      // upper part never rewritten
+            RCN_HIP(hipStreamSynchronize(st));      // `ts` leaves scope
+        }
         RCN_HIP(hipStreamSynchronize(st));      // `stage` leaves scope
     }
     RCN_HIP(hipMemsetAsync(p_flag, 0, 24 * sizeof(int), st));
@@ -1667,8 +1721,8 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     RCN_HIP(hipMemsetAsync(vecs, 0, sizeof(double) * 12 * nvec, st));
     RCN_HIP(hipMemsetAsync(d.S, 0, sizeof(double) * (size_t)npad * npad, st));   // upper part / padding never rewritten
     RCN_HIP(hipMemsetAsync(d.Linv, 0, sizeof(double) * cws.linv, st));   // upper triangles of the tile inverses stay zero
-    if (nblk > 2) RCN_HIP(hipMemsetAsync(SI, 0, sizeof(double) * cws.si, st));   // blocks above a super-block inverse's diagonal stay zero (a column-0 pass reads 64 columns of one)
-    { int rcm = rcn_chol_prepare(ctx); if (!rcm) rcm = rcn_chol_plan(ctx, nblk); if (rcm) return rcm; }
+    if (nblk_f > 2) RCN_HIP(hipMemsetAsync(SI, 0, sizeof(double) * cws.si, st));   // blocks above a super-block inverse's diagonal stay zero (a column-0 pass reads 64 columns of one)
+    { int rcm = rcn_chol_prepare(ctx); if (!rcm) rcm = rcn_chol_plan(ctx, nblk_f); if (rcm) return rcm; }
     uint64_t plain_token = 0;
     if (!res && no > 0) {
         const bool same = ctx->ba_graph_nc == nc && ctx->ba_graph_np == np && ctx->ba_graph_cam.size() == (size_t)no &&
@@ -1815,6 +1869,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
     const int dgrid = (std::max(n, 3 * np) + 255) / 256;
     k_ba_diag<<<std::max(dgrid, 1), 256, 0, st>>>(d, 0, 0.0, 0.0, opt->jacobi_scaling);
     RCN_HIP(hipGetLastError());
+    if (tied) RCN_HIP(rcn_tied_scale(T, d.Uraw, d.sc, opt->jacobi_scaling, st));      // tied: one scale per group column, from the members' summed diagonal
     if (pairs_build) { const int rcp = build_pairs(); if (rcp) return rcp; }
     RCN_HIP(read_scal(1, true));
     cost = hs[0];
@@ -1836,11 +1891,16 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
             // (whenever the gradient is due, so is the LM diagonal -- an accepted step, or the start -- and both come from the raw blocks
             //  of the evaluation just queued: one launch; a loop that ends below has written a diagonal nobody reads)
             // (... and with the diagonal the landmarks' damped blocks at the radius the next step will use: k_ba_point_solve's launch)
+            if (tied) {      // tied: the gradient of a group column is the members' sum; the diagonal and the landmark blocks by their plain launches below
+                RCN_HIP(rcn_tied_gradmax(T, d.gcraw, d.gpraw, np, d.intr, d.scal + 12, st));
+                diag_fresh = points_fresh = false;
+            } else {
             k_ba_gradmax<<<std::max(1, std::min(1024, (std::max(std::max(nc, n), 3 * np) + 255) / 256)), 256, 0, st>>>(d, d.scal + 12, reuse_diag ? 0 : 2,
                                                                                                                      opt->min_lm_diagonal, opt->max_lm_diagonal, 1.0 / radius);
             RCN_HIP(hipGetLastError());
             diag_fresh = !reuse_diag;
             points_fresh = !reuse_diag;
+            }
             need_gradient = false;
             grad_pending = true;
         }
@@ -1860,6 +1920,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         if (!reuse_diag && !diag_fresh) {
             k_ba_diag<<<std::max(dgrid, 1), 256, 0, st>>>(d, 1, opt->min_lm_diagonal, opt->max_lm_diagonal, opt->jacobi_scaling);
             RCN_HIP(hipGetLastError());
+            if (tied) RCN_HIP(rcn_tied_diag(T, d.Uraw, d.sc, d.dgc, opt->min_lm_diagonal, opt->max_lm_diagonal, st));      // tied: the clamp of the sum, added by the fold; the members' own entries zero
         }
         diag_fresh = false;
         const double ir = 1.0 / radius;
@@ -1867,13 +1928,20 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         // [0] breakdown / gate flag, [2..7] progress counters of the factorisation's streams.  In the default form (gather Schur build, the
         // right-hand side as row n of the padded system) the flag words, the padded rows and the right-hand-side row are all written by
         // the Schur diagonal launch (its cameras' workgroups and the workgroups behind them), and nothing has to be cleared up front: the Schur kernels write every entry of rhs below n.
-        const bool rhs_row = npad > n && !ctx->ba_trsv_fwd;
-        const bool fused_finish = gather && rhs_row;
-        const bool chain = rcn_chol_bwd_one_launch(ctx, nblk);      // backward substitution as one launch
+        // (tied: the Schur launches write the per-camera system, the factorisation reads its fold -- no fused shortcut, the plain launches)
+        const bool rhs_row = npad_f > n_f && !ctx->ba_trsv_fwd;
+        const bool fused_finish = gather && rhs_row && !tied;
+        const bool chain = rcn_chol_bwd_one_launch(ctx, nblk_f);      // backward substitution as one launch
+        BaDev dt = d;      // tied: the folded system as the plain finishing kernels take it
+        if (tied) { dt.n = n_f; dt.npad = npad_f; dt.S = T.S2; dt.rhs = T.rhs2; dt.yc = yc2; }
         if (!fused_finish) {
             if (!gather) RCN_HIP(hipMemsetAsync(Sb, 0, sizeof(double) * 100 * (size_t)nc * nc, st));
             if (npad > n) RCN_HIP(hipMemsetAsync(d.S + (size_t)n * npad, 0, sizeof(double) * (size_t)(npad - n) * npad, st));
             RCN_HIP(hipMemsetAsync(d.rhs, 0, sizeof(double) * npad, st));
+            if (tied) {
+                if (npad_f > n_f) RCN_HIP(hipMemsetAsync(T.S2 + (size_t)n_f * npad_f, 0, sizeof(double) * (size_t)(npad_f - n_f) * npad_f, st));
+                RCN_HIP(hipMemsetAsync(T.rhs2, 0, sizeof(double) * npad_f, st));
+            }
         }
         if (np > 0 && !points_fresh) k_ba_point_solve<<<(np + 127) / 128, 128, 0, st>>>(d, ir);      // (a step behind an accepted one: done in k_ba_gradmax's launch)
         points_fresh = false;
@@ -1891,13 +1959,18 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
             const int fin_blocks = fused_finish ? (int)(((size_t)(npad - n) * npad + 1023) / 1024) : 0;
             if (nc < 128) { k_ba_schur_diag_mfma<12><<<nc * csplit + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, csplit, fin); diag_smb = 12; }      // (few cameras: latency-bound, deep gathers)
             else { k_ba_schur_diag_mfma<4><<<nc + fin_blocks, 1024, 0, st>>>(d, pk_off, pk_list, ir, 1, fin); diag_smb = 4; }
-            if (!fused_finish && npad > n) k_ba_S_pad<<<(npad - n + 127) / 128, 128, 0, st>>>(d);
+            if (!fused_finish && !tied && npad > n) k_ba_S_pad<<<(npad - n + 127) / 128, 128, 0, st>>>(d);
         } else {
             if (np > 0) k_ba_schur<<<np, std::min(256, std::max(64, 64 * ((kmax * kmax + 7) / 8))), 0, st>>>(d, Sb);
             k_ba_S_assemble<<<nc + 1, 256, 0, st>>>(d, Sb, ir);
             k_ba_cam_rhs<<<nc, 64, 0, st>>>(d);
         }
-        if (rhs_row && !fused_finish) k_ba_S_rhs_row<<<(n + 1 + 255) / 256, 256, 0, st>>>(d);
+        if (tied) {
+            // the fold: S' = P' S P with the groups' damping, b' = P' b; then padding and the right-hand-side row as for any system
+            RCN_HIP(rcn_tied_fold(T, d.S, d.rhs, ir, st));
+            if (npad_f > n_f) k_ba_S_pad<<<(npad_f - n_f + 127) / 128, 128, 0, st>>>(dt);
+            if (rhs_row) k_ba_S_rhs_row<<<(n_f + 1 + 255) / 256, 256, 0, st>>>(dt);
+        } else if (rhs_row && !fused_finish) k_ba_S_rhs_row<<<(n + 1 + 255) / 256, 256, 0, st>>>(d);
         RCN_HIP(hipGetLastError());
         if (phase_times) RCN_HIP(hipEventRecord(ctx->ba_tev[1], st));
         if (probe && iter == probe->iteration) {
@@ -1925,14 +1998,15 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         }
         // Dense Cholesky of the padded system and the triangular solves behind it (chol.h).  A hand-off between its streams that times out raises flag 3, read
         // below with the step's scalars: the factorisation is then repeated on ONE stream, and every later one runs that way (ctx->chol.safe).  Same bits either way.
-        const CholSystem sys = {d.S, d.L, d.Linv, SI, d.flag, d.rhs, d.yc, n, npad, nblk, rhs_row, chain, fused_finish};
+        const CholSystem sys = {dt.S, d.L, d.Linv, SI, d.flag, dt.rhs, dt.yc, n_f, npad_f, nblk_f, rhs_row, chain, fused_finish};
         // (up to two blocks there is no panel rest, no column rest and no bulk update: nothing for the other two streams to do)
-        RCN_HIP(rcn_chol_factorise(ctx, sys, ctx->chol.safe || nblk <= 2));
+        RCN_HIP(rcn_chol_factorise(ctx, sys, ctx->chol.safe || nblk_f <= 2));
         if (phase_times) RCN_HIP(hipEventRecord(ctx->ba_tev[2], st));
         // (rhs_row + chain, the default: the substitution reads y out of the factor's last row itself; k_ba_y_from_row remains for the
         //  per-step kernels and the other ways to build the system)
-        if (rhs_row && !(chain && fused_finish)) k_ba_y_from_row<<<(npad + 255) / 256, 256, 0, st>>>(d, chain ? 1 : 0);
+        if (rhs_row && !(chain && fused_finish)) k_ba_y_from_row<<<(npad_f + 255) / 256, 256, 0, st>>>(dt, chain ? 1 : 0);
         RCN_HIP(rcn_chol_substitute(ctx, sys));
+        if (tied) RCN_HIP(rcn_tied_expand(T, T.rhs2, d.rhs, st));      // delta = P delta': every member carries its group's step
         {   // the solution sits in d.rhs: the two kernels that read it take it from there (round 3 copied it to d.yc first)
             BaDev dx = d;
             dx.yc = d.rhs;
@@ -1945,6 +2019,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
         // scal: [3] |dx|^2  [4] |x|^2  [5] g.delta, also in [8]  [6] non-finite count, also in [9]
         k_ba_plus<<<pbk, 256, 0, st>>>(d, 1.0, d.partial, pbk, fin(d.scal + 3, 1.0, 2, false, nullptr, d.scal + 8));
         RCN_HIP(hipGetLastError());
+        if (tied) RCN_HIP(rcn_tied_norms(T, d.intr, d.intr2, d.scal, st));      // |dx|, |x| with a tied parameter counted once
         RCN_HIP(eval(false, d.poses2, d.intr2, d.pts2, 1, true));       // + the factorisation's flag word into scal[13]
         if (phase_times) RCN_HIP(hipEventRecord(ctx->ba_tev[3], st));
         RCN_HIP(read_scal(14, true));
@@ -2016,6 +2091,7 @@ int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_option
             bool found = false;
             auto trial = [&](double alpha) -> hipError_t {   // candidate, its cost and the step norms at alpha
                 k_ba_plus<<<pbk, 256, 0, st>>>(d, alpha, d.partial, pbk, fin(d.scal + 3, 1.0, 2, false, nullptr, d.scal + 14));      // ([14], [15]: nobody reads them here)
+                if (tied) { const hipError_t et = rcn_tied_norms(T, d.intr, d.intr2, d.scal, st); if (et != hipSuccess) return et; }
                 hipError_t e = eval(false, d.poses2, d.intr2, d.pts2, 1);
                 if (e != hipSuccess) return e;
                 e = read_scal(5);

@@ -15,12 +15,14 @@
 // Appending a view costs the bytes of what is new; nothing is re-packed.  The arithmetic of a session solve is the
 // arithmetic of rcn_ba_solve on the same problem (same kernels, same order): results are identical bit for bit.
 #include "rcn_internal.h"
+#include "ba_tied.h"
 
 #include <algorithm>
 #include <climits>
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <set>
 #include <unordered_map>
 
 namespace {
@@ -80,6 +82,8 @@ struct rcn_ba_session {
     std::vector<uint8_t> last_inlier;                // result of the last validity sweep (for remove_outliers)
     bool have_inlier = false;
     rcn_ba_loss loss{RCN_BA_LOSS_TRIVIAL, 0, 0.0};   // rcn_ba_session_set_loss: the loss of every later solve (trivial: none)
+    std::vector<int32_t> groups;                     // rcn_ba_session_set_groups: per camera, -1 = its own intrinsics (shorter than the camera count: the rest are -1; empty: none)
+    std::vector<int32_t> loc_groups;                 // ... mapped through a local solve's camera map
     DevBuf cams_dev;                                 // rcn_ba_session_loss_report: the cameras' 6 + 6 numbers, uploaded per call
     BaLocalWs loc;                                   // rcn_ba_session_solve_local / _covisible: the sub-problem's arrays (ba_local.hip)
     std::vector<double> loc_poses, loc_intr;         // ... its cameras' 6 + 6 numbers
@@ -258,8 +262,23 @@ int rcn_ba_session_solve(rcn_ba_session *s, const rcn_ba_options *options, rcn_b
     BaResident res{static_cast<double *>(s->pts.p), s->uv.as<double>(), s->ocam.as<int>(), s->opt.as<int>(),
                    ((uint64_t)s->id << 32) | s->version};
     s->have_inlier = false;
+    if (!s->groups.empty()) s->groups.resize((size_t)nc, -1);      // (cameras added since the groups were set)
     return rcn_int_ba_solve(ctx, &pb, &o, summary, &res,     // poses / intrinsics come back into the host mirror, points stay in HBM
-                            s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr);
+                            s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr, nullptr, nullptr, nullptr, s->groups.empty() ? nullptr : s->groups.data());
+}
+
+int rcn_ba_session_set_groups(rcn_ba_session *s, const int32_t *cam_group, int32_t n)
+{
+    if (!s) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!cam_group && n == 0) { s->groups.clear(); return RCN_OK; }
+    const int32_t nc = (int32_t)(s->poses.size() / 6);
+    if (!cam_group || n != nc) { ctx->set_error("rcn_ba_session_set_groups: " + std::to_string(n) + " entries for " + std::to_string(nc) + " cameras"); return RCN_ERR_ARG; }
+    for (int32_t c = 0; c < n; ++c)
+        if (cam_group[c] < -1) { ctx->set_error("rcn_ba_session_set_groups: camera " + std::to_string(c) + ": group id " + std::to_string(cam_group[c]) + " is below -1"); return RCN_ERR_ARG; }
+    s->groups.assign(cam_group, cam_group + n);
+    return RCN_OK;
 }
 
 // A local adjustment: the cameras free_cams[] move, with the landmarks they see; every other camera that sees one of those landmarks
@@ -296,6 +315,14 @@ int rcn_ba_session_solve_local(rcn_ba_session *s, const int32_t *free_cams, int3
     if (w.n_points == 0) { ctx->set_error(std::string(who) + ": the free cameras have no observation: the reduced system has no free parameter"); return RCN_ERR_ARG; }
     const int32_t ncl = w.n_cams;
     s->loc_poses.resize(6 * (size_t)ncl); s->loc_intr.resize(6 * (size_t)ncl); s->loc_const.resize((size_t)ncl);
+    // a group moves only when the window frees ALL its members: one that has a member outside -- a constant camera of the sub-problem or
+    // a camera that is not part of it at all -- is held, or its members would leave with different intrinsics
+    std::set<int32_t> held_ids;
+    if (!s->groups.empty()) {
+        s->loc_groups.assign((size_t)ncl, -1);
+        for (size_t c = 0; c < s->groups.size() && c < (size_t)nc; ++c)
+            if (s->groups[c] >= 0 && !s->loc_free[c]) held_ids.insert(s->groups[c]);
+    }
     int32_t n_const = 0;
     for (int32_t l = 0; l < ncl; ++l) {
         const int32_t c = w.h_cam_map[l];
@@ -303,6 +330,8 @@ int rcn_ba_session_solve_local(rcn_ba_session *s, const int32_t *free_cams, int3
         std::copy(s->poses.begin() + 6 * (size_t)c, s->poses.begin() + 6 * (size_t)c + 6, s->loc_poses.begin() + 6 * (size_t)l);
         std::copy(s->intr.begin() + 6 * (size_t)c, s->intr.begin() + 6 * (size_t)c + 6, s->loc_intr.begin() + 6 * (size_t)l);
         s->loc_const[l] = s->loc_free[c] ? 0 : 1;
+        if (!s->groups.empty() && (size_t)c < s->groups.size() && s->groups[c] >= 0)
+            s->loc_groups[l] = held_ids.count(s->groups[c]) ? ba_tied::HELD : s->groups[c];
         n_const += s->loc_const[l];
     }
     if (info_out) { info_out[0] = ncl; info_out[1] = n_const; info_out[2] = w.n_points; info_out[3] = w.n_obs; }
@@ -313,7 +342,8 @@ int rcn_ba_session_solve_local(rcn_ba_session *s, const int32_t *free_cams, int3
                       s->h_uv.data(), w.h_ocam.data(), w.h_opt.data()};      // (obs_uv: the solver reads the resident copy; the pointer only has to be there)
     BaResident res{w.pts.as<double>(), w.uv.as<double>(), w.ocam.as<int>(), w.opt.as<int>(), 0};
     s->have_inlier = false;
-    rc = rcn_int_ba_solve(ctx, &pb, &o, summary, &res, s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr, nullptr, nullptr, s->loc_const.data());
+    rc = rcn_int_ba_solve(ctx, &pb, &o, summary, &res, s->loss.kind != RCN_BA_LOSS_TRIVIAL ? &s->loss : nullptr, nullptr, nullptr, s->loc_const.data(),
+                          s->groups.empty() ? nullptr : s->loc_groups.data());
     if (rc != RCN_OK && rc != RCN_ERR_NUMERIC) return rc;     // (a failed solve has still written its last accepted point, as rcn_ba_session_solve leaves it)
     const double t2 = now();
     const int rcs = rcn_int_ba_local_scatter(ctx, w, static_cast<double *>(s->pts.p));

@@ -8,9 +8,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.13 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.14 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.13 (gfx950)";
+    return "reconstructor_amd 0.14 (gfx950)";
 #endif
 }
 

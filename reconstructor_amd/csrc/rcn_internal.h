@@ -326,7 +326,7 @@ struct BaResident {
 };
 int rcn_int_ba_solve(rcn_ctx *ctx, const rcn_ba_problem *pb, const rcn_ba_options *opt, rcn_ba_summary *sum, const BaResident *res,
                      const rcn_ba_loss *loss = nullptr, rcn_ba_loss_report *report = nullptr, double *weights_host = nullptr,
-                     const uint8_t *cam_constant = nullptr);
+                     const uint8_t *cam_constant = nullptr, const int32_t *cam_group = nullptr);
 // ba_local.hip, ctx->mu held: the sub-problem of a local adjustment cut out of a session's resident arrays (rcn_ba_session_solve_local), the
 // scatter of its solved points, and the covisibility counts (rcn_ba_session_covisible).  The workspace belongs to the session; it only grows.
 struct BaLocalWs {

@@ -52,6 +52,25 @@ template <class M> inline void angleAxisToPose(const double *w6, M &T)
 }
 }  // namespace detail
 
+namespace detail {
+// cam_group of rcn_ba_solve_tied in imgIdxOrder (empty: no groups); every member of a group takes the six intrinsics of the group's first view
+inline std::vector<int32_t> packGroups(const std::unordered_map<int, int> &imgIdx2group, const std::vector<int> &imgIdxOrder, std::vector<double> &intr)
+{
+    std::vector<int32_t> grp;
+    if (imgIdx2group.empty()) return grp;
+    grp.assign(imgIdxOrder.size(), -1);
+    std::unordered_map<int, size_t> first;
+    for (size_t l = 0; l < imgIdxOrder.size(); ++l) {
+        const auto it = imgIdx2group.find(imgIdxOrder[l]);
+        if (it == imgIdx2group.end() || it->second < 0) continue;
+        grp[l] = it->second;
+        const auto f = first.emplace(it->second, l);
+        if (!f.second) std::copy(intr.begin() + 6 * f.first->second, intr.begin() + 6 * f.first->second + 6, intr.begin() + 6 * l);
+    }
+    return grp;
+}
+}  // namespace detail
+
 class BundleAdjuster {
 public:
     explicit BundleAdjuster(rcn_ctx *ctx = nullptr) : ctx_(ctx), owned_(false)
@@ -68,6 +87,14 @@ public:
     // robust costs, and lossReport() the plain residual statistics of the last adjust (zeros while no loss is set).
     void setLoss(int kind, double scale) { loss_ = rcn_ba_loss{(int32_t)kind, 0, scale}; }
     const rcn_ba_loss_report &lossReport() const { return report_; }
+
+    // Shared intrinsics for every later adjust (rcn_ba_solve_tied): images with the same group number >= 0 were taken by ONE physical
+    // camera, whose fx, fy, k1, k2 are one set of unknowns wherever the reference frees the intrinsics (ten views or more); an image that
+    // is not in the map, or maps to -1, keeps intrinsics of its own.  The members of a group must enter a solve with identical
+    // intrinsics: the adapter gives every member the PinholeCamera values of the group's first view in imgIdxOrder (a view registered
+    // since the last adjust takes the group's refined values), and writes the solved values back into every member's PinholeCamera.
+    // An empty map switches it off.
+    void setSharedIntrinsics(const std::unordered_map<int, int> &imgIdx2group) { groups_ = imgIdx2group; }
 
     template <class Pose4>
     std::unordered_map<int, int> adjust(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
@@ -89,6 +116,7 @@ public:
             for (int i = 0; i < 3; ++i) extr[6 * l + 3 + i] = T(i, 3);
             global2local[g] = l;
         }
+        const std::vector<int32_t> grp = detail::packGroups(groups_, imgIdxOrder, intr);
         std::vector<double> uv;
         std::vector<int32_t> cam, pt;
         for (size_t j = 0; j < landmarks.size(); ++j) {                     // :65-97, landmark-major
@@ -107,7 +135,9 @@ public:
         rcn_ba_default_options(nCams, &opt);                                // :99-142
         const bool robust = loss_.kind != RCN_BA_LOSS_TRIVIAL;
         report_ = rcn_ba_loss_report{};
-        const int rc = rcn_ba_solve_robust(ctx_, &pb, &opt, robust ? &loss_ : nullptr, &summary, robust ? &report_ : nullptr, nullptr);   // no loss: rcn_ba_solve
+        const int rc = grp.empty()
+            ? rcn_ba_solve_robust(ctx_, &pb, &opt, robust ? &loss_ : nullptr, &summary, robust ? &report_ : nullptr, nullptr)   // no loss: rcn_ba_solve
+            : rcn_ba_solve_tied(ctx_, &pb, &opt, robust ? &loss_ : nullptr, nullptr, grp.data(), &summary, robust ? &report_ : nullptr, nullptr);
         if (rc != RCN_OK && rc != RCN_ERR_NUMERIC)                          // the reference ignores Ceres' summary (:145-147)
             throw std::runtime_error(std::string("rcn_ba_solve_robust: ") + rcn_last_error(ctx_));
         for (size_t j = 0; j < landmarks.size(); ++j) {                     // :150-155
@@ -131,6 +161,7 @@ private:
     bool owned_;
     rcn_ba_loss loss_{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
     rcn_ba_loss_report report_{};
+    std::unordered_map<int, int> groups_;
 };
 
 }  // namespace reconstructor::Core

@@ -50,6 +50,10 @@ public:
         return r;
     }
 
+    // BundleAdjuster::setSharedIntrinsics over the session (rcn_ba_session_set_groups): kept across adjusts and rebuilds.  A global
+    // adjust ties every group; a local one moves a group only when its window frees all the group's views, and holds it otherwise.
+    void setSharedIntrinsics(const std::unordered_map<int, int> &imgIdx2group) { groups_ = imgIdx2group; }
+
     template <class Pose4>
     std::unordered_map<int, int> adjust(std::unordered_map<int, std::vector<FeaturePtr<>>> &features,
                                         std::vector<Landmark> &landmarks,
@@ -146,12 +150,14 @@ private:
             detail::rotationToAngleAxis(T, &extr[6 * l]);
             for (int i = 0; i < 3; ++i) extr[6 * l + 3 + i] = T(i, 3);
         }
+        const std::vector<int32_t> grp = detail::packGroups(groups_, imgIdxOrder, intr);
         for (int l = (int)order_.size(); l < nCams; ++l) {
             int32_t idx = -1;
             check(rcn_ba_session_add_camera(session_, &extr[6 * l], &intr[6 * l], &idx), "rcn_ba_session_add_camera");
             order_.push_back(imgIdxOrder[l]);
         }
         check(rcn_ba_session_cameras(session_, nullptr, nullptr, extr.data(), intr.data()), "rcn_ba_session_cameras");
+        check(rcn_ba_session_set_groups(session_, grp.empty() ? nullptr : grp.data(), (int32_t)grp.size()), "rcn_ba_session_set_groups");
 
         // new landmarks, then the new tail of every track (push_back order)
         const size_t known = tracks_.size();
@@ -242,6 +248,7 @@ private:
     int rebuilds_ = 0;
     std::vector<int> window_;                                   // image indices freed by the last adjustLocal
     rcn_ba_loss loss_{RCN_BA_LOSS_TRIVIAL, 0, 0.0};
+    std::unordered_map<int, int> groups_;
 };
 
 }  // namespace reconstructor::Core

@@ -19,6 +19,7 @@
 // Exit code: 0 when every case ran, 1 on the first HIP error or a solve that returned an error, 2 on a case it cannot read or write.
 #include "../reconstructor_amd/csrc/chol.hip"
 #include "../reconstructor_amd/csrc/ba.hip"
+#include "../reconstructor_amd/csrc/ba_tied.hip"
 #include <fstream>
 #include <sstream>
 
