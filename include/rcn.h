@@ -55,7 +55,7 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * classification rcn_twoview_geometry* with their option structs; 13 -> 14 shared intrinsics: rcn_ba_solve_tied,
  * rcn_ba_session_set_groups).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 14
+#define RCN_ABI_REVISION 15
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -1311,6 +1311,77 @@ int  rcn_cloud_vertices_device(rcn_ctx *ctx, const double *xyz_dev /*[L][3]*/, c
 /* Host code: a PLY file of those records (property float x / y / z, uchar red / green / blue / alpha), ASCII or
  * binary_little_endian.  RCN_ERR_IO when the file cannot be written. */
 int  rcn_cloud_write_ply(const char *path, const void *vertices_host, int64_t n_vertices, int32_t binary);
+
+/* ---- ORB: FeatureClassic's second detector (the cv::ORB::create() of FeatureDetector.cpp:9, :19) ----------------------
+ * Oriented FAST and rotated BRIEF with cv::ORB::create()'s defaults, restated in tests/orb_ref.py (what
+ * could not be pinned against OpenCV itself is listed in section 1).  Fixed: firstLevel 0, WTA_K 2, Harris score, patch 31.
+ * Integer arithmetic throughout, except the Harris response and the patch direction, which are single correctly rounded fp64
+ * operations without contraction: every output equals the restatement bit for bit (angle, informative only: 1 fp32 ulp).
+ * An image's result does not depend on the batch, the chunking, the strides, the input type of equal values or the run.
+ *
+ * Packed byte pyramid of one image: level l is level_h[l] x level_w[l] bytes at level_offset[l] (a multiple of 16),
+ * bytes_per_image in all; level 0 is the image (a float image converted round-half-even, clamped), level l is level l - 1
+ * through the 8-bit bilinear resize of rcn_img_prepare_device.  Score maps (rcn_orb_fast_device) have the same layout.
+ * rcn_orb_layout and rcn_orb_default_pattern are pure host code (no device needed).
+ *
+ * Capacity: FAST corners after the strict 3 x 3 maximum are at most one per 2 x 2 pixels, and the lists hold that many, so
+ * they cannot overflow.  Of those, a level keeps the ones at or above its 2 * quota-th largest FAST score; when ties make
+ * that more than RCN_ORB_MAX_SURVIVORS on one level the image reports counts = -1 and no rows. */
+#define RCN_ORB_MAX_LEVELS 16
+#define RCN_ORB_MAX_SURVIVORS 8192
+#define RCN_ORB_INPUT_F32 0              /* pixels on the 0..255 scale, finite */
+#define RCN_ORB_INPUT_U8  1
+typedef struct {
+    int32_t nfeatures;                   /* 500, >= 1 */
+    int32_t nlevels;                     /* 8, 1..RCN_ORB_MAX_LEVELS */
+    int32_t edge_threshold;              /* 31, 22..4096: the rotated tests reach 22 pixels */
+    int32_t fast_threshold;              /* 20, 1..254 */
+    double  scale_factor;                /* 1.2, > 1 and <= 4 */
+    const int8_t *pattern;               /* host: 256 tests (x0, y0, x1, y1), every |coordinate| <= 15; NULL: rcn_orb_default_pattern */
+} rcn_orb_options;
+typedef struct {
+    int32_t n_levels, reserved;
+    int32_t level_h[RCN_ORB_MAX_LEVELS], level_w[RCN_ORB_MAX_LEVELS];
+    int32_t quota[RCN_ORB_MAX_LEVELS];   /* cv::ORB's geometric split of nfeatures */
+    int32_t active[RCN_ORB_MAX_LEVELS];  /* 0: min(h, w) <= 2 * edge_threshold, the level yields no keypoints */
+    float   scale[RCN_ORB_MAX_LEVELS];   /* float(pow(double(scale_factor), l)) */
+    int64_t level_offset[RCN_ORB_MAX_LEVELS];
+    int64_t bytes_per_image;
+} rcn_orb_pyramid_layout;
+void rcn_orb_default_options(rcn_orb_options *opt);
+const int8_t *rcn_orb_default_pattern(void);   /* 1024 bytes: a BRIEF pattern of Gaussian points clipped to +-13 (tests/orb_ref.py::default_pattern) */
+/* opt == NULL: the defaults.  RCN_ERR_ARG: an option out of range, H or W < 1 or > 65535 (a keypoint's level coordinates are
+ * packed into 16 bits each), H W > 2^31 - 1, an empty level, a level
+ * that halves the one before it on both axes (cv::resize takes another path there), a pattern coordinate beyond +-15. */
+int  rcn_orb_layout(int32_t H, int32_t W, const rcn_orb_options *opt, rcn_orb_pyramid_layout *out);
+/* images per pass over the ctx's workspace (<= 0: as many as fit its default cap of 1 GiB) */
+int  rcn_orb_set_chunk_images(rcn_ctx *ctx, int32_t images);
+/* images_dev: n grey images [H][W] addressed by ELEMENT strides (image, y, x), as the SIFT calls read them.
+ * pyr_out_dev: [n][bytes_per_image].  Asynchronous on the ctx stream (the resize tables of a new size are uploaded first: waits once). */
+int  rcn_orb_pyramid_device(rcn_ctx *ctx, const void *images_dev, int32_t input_dtype, int64_t stride_img, int64_t stride_y,
+                            int64_t stride_x, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt, uint8_t *pyr_out_dev);
+/* For inspection: the FAST-9/16 score of every pixel of every level (the largest t >= fast_threshold at which it is still a
+ * corner, 0 for none and within 3 pixels of the border), before the 3 x 3 maximum.  scores_out_dev: [n][bytes_per_image]. */
+int  rcn_orb_fast_device(rcn_ctx *ctx, const uint8_t *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt,
+                         uint8_t *scores_out_dev);
+/* Keypoints in ascending order of (level, y, x); counts[i] is the uncapped number (it may exceed nfeatures: ties are kept) --
+ * when it exceeds K the K largest by (response descending, canonical rank ascending) are emitted, still in canonical order.
+ * xy = (x, y) * scale[level], size = 31 * scale[level], octave = level, angle in degrees in [0, 360), response the Harris
+ * response rounded to fp32.  Rows past min(counts[i], K): xy and xy_int (-1, -1), the other fields 0. */
+int  rcn_orb_detect_device(rcn_ctx *ctx, const uint8_t *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt, int32_t K,
+                           float *xy_dev /*[n][K][2]*/, int32_t *xy_int_dev /*[n][K][2]*/, float *size_dev /*[n][K]*/,
+                           float *angle_dev /*[n][K]*/, float *response_dev /*[n][K]*/, int32_t *octave_dev /*[n][K]*/,
+                           int32_t *counts_dev /*[n]*/);
+/* 32 floats in 0..255 per keypoint (the bytes of the descriptor converted to CV_32F, FeatureDetector.cpp:24), rows past
+ * min(counts[i], K) zero; bytes_out_dev (may be NULL): the same bytes packed, [n][K][32]. */
+int  rcn_orb_describe_device(rcn_ctx *ctx, const uint8_t *pyr_dev, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt, int32_t K,
+                             const float *xy_dev, const int32_t *octave_dev, const int32_t *counts_dev, float *rows_out_dev /*[n][K][32]*/,
+                             uint8_t *bytes_out_dev);
+/* The three in one call, the pyramid in the ctx's workspace: bit for bit the three calls. */
+int  rcn_orb_detect_and_compute_device(rcn_ctx *ctx, const void *images_dev, int32_t input_dtype, int64_t stride_img, int64_t stride_y,
+                                       int64_t stride_x, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt, int32_t K,
+                                       float *xy_dev, int32_t *xy_int_dev, float *size_dev, float *angle_dev, float *response_dev,
+                                       int32_t *octave_dev, int32_t *counts_dev, float *rows_out_dev, uint8_t *bytes_out_dev);
 
 #ifdef __cplusplus
 }

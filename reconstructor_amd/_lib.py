@@ -48,6 +48,8 @@ SYMBOLS = [
     "rcn_sp_net_create", "rcn_sp_net_destroy", "rcn_sp_net_set_chunk_images", "rcn_sp_net_forward_device", "rcn_sp_net_detect_device",
     "rcn_sift_default_options", "rcn_sift_layout", "rcn_sift_set_chunk_images", "rcn_sift_pyramid_device", "rcn_sift_candidates_device", "rcn_sift_detect_device",
     "rcn_sift_describe_device", "rcn_sift_detect_and_compute_device",
+    "rcn_orb_default_options", "rcn_orb_default_pattern", "rcn_orb_layout", "rcn_orb_set_chunk_images", "rcn_orb_pyramid_device", "rcn_orb_fast_device",
+    "rcn_orb_detect_device", "rcn_orb_describe_device", "rcn_orb_detect_and_compute_device",
     "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
@@ -143,6 +145,17 @@ class SiftLayout(C.Structure):
                 ("base_sigma", C.c_double), ("oct_h", C.c_int32 * 16), ("oct_w", C.c_int32 * 16),
                 ("layer_sigma", C.c_double * 8), ("layer_taps", C.c_int32 * 8), ("layer_offset", (C.c_int64 * 8) * 16),
                 ("floats_per_image", C.c_int64)]
+
+
+class OrbOptions(C.Structure):
+    _fields_ = [("nfeatures", C.c_int32), ("nlevels", C.c_int32), ("edge_threshold", C.c_int32), ("fast_threshold", C.c_int32),
+                ("scale_factor", C.c_double), ("pattern", C.c_void_p)]
+
+
+class OrbLayout(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("reserved", C.c_int32), ("level_h", C.c_int32 * 16), ("level_w", C.c_int32 * 16),
+                ("quota", C.c_int32 * 16), ("active", C.c_int32 * 16), ("scale", C.c_float * 16), ("level_offset", C.c_int64 * 16),
+                ("bytes_per_image", C.c_int64)]
 
 
 class ImgOptions(C.Structure):
@@ -310,6 +323,26 @@ def load():
     L.rcn_sift_describe_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(SiftOptions), i32, vp, vp, vp, vp, vp, vp]
     L.rcn_sift_detect_and_compute_device.restype = C.c_int
     L.rcn_sift_detect_and_compute_device.argtypes = sift_img + [i32] + sift_kp + [vp]
+    L.rcn_orb_default_options.restype = None
+    L.rcn_orb_default_options.argtypes = [C.POINTER(OrbOptions)]
+    L.rcn_orb_default_pattern.restype = C.POINTER(C.c_int8)
+    L.rcn_orb_default_pattern.argtypes = []
+    L.rcn_orb_layout.restype = C.c_int
+    L.rcn_orb_layout.argtypes = [i32, i32, C.POINTER(OrbOptions), C.POINTER(OrbLayout)]
+    L.rcn_orb_set_chunk_images.restype = C.c_int
+    L.rcn_orb_set_chunk_images.argtypes = [vp, i32]
+    orb_img = [vp, vp, i32, i64, i64, i64, i32, i32, i32, C.POINTER(OrbOptions)]       # ctx, images, dtype, strides, n H W, options
+    orb_pyr = [vp, vp, i32, i32, i32, C.POINTER(OrbOptions)]                           # ctx, pyramids, n H W, options
+    L.rcn_orb_pyramid_device.restype = C.c_int
+    L.rcn_orb_pyramid_device.argtypes = orb_img + [vp]
+    L.rcn_orb_fast_device.restype = C.c_int
+    L.rcn_orb_fast_device.argtypes = orb_pyr + [vp]
+    L.rcn_orb_detect_device.restype = C.c_int
+    L.rcn_orb_detect_device.argtypes = orb_pyr + [i32] + sift_kp
+    L.rcn_orb_describe_device.restype = C.c_int
+    L.rcn_orb_describe_device.argtypes = orb_pyr + [i32, vp, vp, vp, vp, vp]
+    L.rcn_orb_detect_and_compute_device.restype = C.c_int
+    L.rcn_orb_detect_and_compute_device.argtypes = orb_img + [i32] + sift_kp + [vp, vp]
     L.rcn_retr_default_options.restype = None
     L.rcn_retr_default_options.argtypes = [C.POINTER(RetrOptions)]
     L.rcn_retr_codebook_train_device.restype = C.c_int

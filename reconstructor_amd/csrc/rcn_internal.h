@@ -189,6 +189,9 @@ struct rcn_ctx {
     int32_t sp_chunk_images = 0;  // images per chunk of SuperPoint's network (rcn_sp_net_set_chunk_images; 0: as many as fit the default cap)
     DevBuf sift_ws, sift_pyr; // sift.hip: candidate / keypoint lists and counters of one chunk of images; the pyramids of rcn_sift_detect_and_compute_device
     int32_t sift_chunk_images = 0;  // images per chunk of the SIFT detector (rcn_sift_set_chunk_images; 0: as many as fit the default cap)
+    DevBuf orb_ws, orb_pyr, orb_tab; // orb.hip: score maps, blurred levels and lists of one chunk of images; the byte pyramids of rcn_orb_detect_and_compute_device; the resize tables
+    int32_t orb_chunk_images = 0;   // images per chunk of the ORB detector (rcn_orb_set_chunk_images; 0: as many as fit the default cap)
+    std::vector<int64_t> orb_tab_key;   // the level sizes the tables in orb_tab were built for
     DevBuf retr_ws, retr_out; // retrieval.hip: assignments, segment sums and counts, the pair mask; global descriptors, similarities and lists of rcn_retr_image_pairs
     DevBuf img_ws;            // imgprep.hip: the resize tables of one call, 8 bytes per output column and row
     std::vector<char> img_stage_host;   // staging of those tables (uploaded asynchronously; img_ev marks the copy)

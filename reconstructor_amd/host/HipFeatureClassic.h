@@ -7,6 +7,9 @@
 //                      holds the 128 floats of the row converted to CV_32F (:24, :30-32)
 //   detectBatch        n images that are in HBM already; the rows stay there, [n][K][128] in a buffer of the caller's (the slot
 //                      of rcn_shard_reserve, for one); only the integer coordinates and the counts come to the host
+//   Detector           the reference's one-line switch (FeatureDetector.cpp:9, :19): Sift (the default, cv::SIFT::create()) or Orb
+//                      (cv::ORB::create() = rcn_orb_detect_and_compute_device): rows of 32 floats, the descriptor's bytes converted
+//                      to CV_32F (:24); setOrbPattern supplies the 256 tests (NULL: the built-in pattern)
 // The reference has no cap on the number of keypoints: when detect finds more than its buffers hold, the buffers grow and
 // the call runs again, as FeatureSuperPointPost::run does.
 #pragma once
@@ -34,13 +37,18 @@ class FeatureClassic {
 public:
     static constexpr int kMemcpyHostToDevice = 1, kMemcpyDeviceToHost = 2;   // hipMemcpyKind
 
-    explicit FeatureClassic(rcn_ctx *ctx = nullptr, int capacity = 4096) : ctx_(ctx), owned_(false)
+    enum class Detector { Sift, Orb };
+
+    explicit FeatureClassic(Detector detector, rcn_ctx *ctx = nullptr, int capacity = 4096) : FeatureClassic(ctx, capacity, detector) {}
+    explicit FeatureClassic(rcn_ctx *ctx = nullptr, int capacity = 4096, Detector detector = Detector::Sift)
+        : ctx_(ctx), owned_(false), orb_(detector == Detector::Orb), dim_(detector == Detector::Orb ? 32 : 128)
     {
         if (!ctx_) {
             if (rcn_create(0, &ctx_) != RCN_OK) throw std::runtime_error("FeatureClassic: no usable gfx950 device");
             owned_ = true;
         }
         rcn_sift_default_options(&opt_);
+        rcn_orb_default_options(&orbOpt_);
         reserve(capacity < 1 ? 1 : capacity);
     }
     ~FeatureClassic()
@@ -51,6 +59,14 @@ public:
     }
     FeatureClassic(const FeatureClassic &) = delete;
     FeatureClassic &operator=(const FeatureClassic &) = delete;
+
+    int descriptorSize() const { return dim_; }
+    // 256 tests (x0, y0, x1, y1) as 1024 signed bytes, every |coordinate| <= 15, copied; nullptr: the built-in pattern again
+    void setOrbPattern(const int8_t *pattern)
+    {
+        if (pattern) { orbPattern_.assign(pattern, pattern + 1024); orbOpt_.pattern = orbPattern_.data(); }
+        else { orbPattern_.clear(); orbOpt_.pattern = nullptr; }
+    }
 
     GreyImage prepImg(const GreyImage &img) const
     {
@@ -78,32 +94,36 @@ public:
         if (bytes && hipMemcpy(img_, src, bytes, kMemcpyHostToDevice)) throw std::runtime_error("FeatureClassic: host to device copy failed");
         int m = 0;
         for (;;) {
-            if (rcn_sift_detect_and_compute_device(ctx_, img_, img.isFloat ? RCN_SIFT_INPUT_F32 : RCN_SIFT_INPUT_U8, (int64_t)pixels, img.cols, 1, 1, img.rows,
-                                                   img.cols, &opt_, cap_, xy_, xyInt_, size_, angle_, resp_, oct_, count_, rows_) != RCN_OK ||
-                rcn_synchronize(ctx_) != RCN_OK)
+            const int rc = orb_ ? rcn_orb_detect_and_compute_device(ctx_, img_, img.isFloat ? RCN_ORB_INPUT_F32 : RCN_ORB_INPUT_U8, (int64_t)pixels, img.cols, 1, 1,
+                                                                    img.rows, img.cols, &orbOpt_, cap_, xy_, xyInt_, size_, angle_, resp_, oct_, count_, rows_, nullptr)
+                                : rcn_sift_detect_and_compute_device(ctx_, img_, img.isFloat ? RCN_SIFT_INPUT_F32 : RCN_SIFT_INPUT_U8, (int64_t)pixels, img.cols, 1, 1,
+                                                                     img.rows, img.cols, &opt_, cap_, xy_, xyInt_, size_, angle_, resp_, oct_, count_, rows_);
+            if (rc != RCN_OK || rcn_synchronize(ctx_) != RCN_OK)
                 throw std::runtime_error(std::string("FeatureClassic::detect: ") + rcn_last_error(ctx_));
             int32_t host = 0;
             copyOut(&host, count_, sizeof(host));
             ++runs_;
-            if (host < 0) throw std::runtime_error("FeatureClassic::detect: more scale-space extrema than the workspace holds");
+            if (host < 0) throw std::runtime_error(orb_ ? "FeatureClassic::detect: more tied FAST corners than the workspace holds"
+                                                        : "FeatureClassic::detect: more scale-space extrema than the workspace holds");
             m = host;
             if (m <= cap_) break;
             reserve(m);
         }
         std::vector<int32_t> xy(2 * (size_t)m + 2);
-        std::vector<float> rows((size_t)m * 128 + 1);
+        const size_t D = (size_t)dim_;
+        std::vector<float> rows((size_t)m * D + 1);
         copyOut(xy.data(), xyInt_, 2 * (size_t)m * sizeof(int32_t));
-        copyOut(rows.data(), rows_, (size_t)m * 128 * sizeof(float));
+        copyOut(rows.data(), rows_, (size_t)m * D * sizeof(float));
         for (int i = 0; i < m; ++i) {
             FeaturePtr<> feat = std::make_shared<Feature<>>();
             feat->featCoord.x = xy[2 * i];
             feat->featCoord.y = xy[2 * i + 1];
-            feat->featDesc.desc.assign(rows.begin() + (size_t)i * 128, rows.begin() + (size_t)(i + 1) * 128);
+            feat->featDesc.desc.assign(rows.begin() + (size_t)i * D, rows.begin() + (size_t)(i + 1) * D);
             features.push_back(feat);
         }
     }
 
-    // imagesDev: n byte images [rows][cols], dense, in HBM; rowsOutDev: [n][K][128] floats in HBM, rows past min(count, K) zero.
+    // imagesDev: n byte images [rows][cols], dense, in HBM; rowsOutDev: [n][K][descriptorSize()] floats in HBM, rows past min(count, K) zero.
     // coords[i]: the integer coordinates of the min(counts[i], K) keypoints emitted for image i; counts[i]: the uncapped number.
     void detectBatch(const uint8_t *imagesDev, int n, int rows, int cols, int K, float *rowsOutDev, std::vector<std::vector<FeatCoord<>>> &coords,
                      std::vector<int> &counts)
@@ -118,8 +138,10 @@ public:
             if (f) (void)hipFree(f);
             throw std::runtime_error("FeatureClassic: out of device memory");
         }
-        const int rc = rcn_sift_detect_and_compute_device(ctx_, imagesDev, RCN_SIFT_INPUT_U8, (int64_t)rows * cols, cols, 1, n, rows, cols, &opt_, K, f, i32,
-                                                          f + 2 * nk, f + 3 * nk, f + 4 * nk, i32 + 2 * nk, i32 + 3 * nk, rowsOutDev);
+        const int rc = orb_ ? rcn_orb_detect_and_compute_device(ctx_, imagesDev, RCN_ORB_INPUT_U8, (int64_t)rows * cols, cols, 1, n, rows, cols, &orbOpt_, K, f, i32,
+                                                                f + 2 * nk, f + 3 * nk, f + 4 * nk, i32 + 2 * nk, i32 + 3 * nk, rowsOutDev, nullptr)
+                            : rcn_sift_detect_and_compute_device(ctx_, imagesDev, RCN_SIFT_INPUT_U8, (int64_t)rows * cols, cols, 1, n, rows, cols, &opt_, K, f, i32,
+                                                                 f + 2 * nk, f + 3 * nk, f + 4 * nk, i32 + 2 * nk, i32 + 3 * nk, rowsOutDev);
         std::vector<int32_t> host(nk * 2 + (size_t)n);
         const bool ok = rc == RCN_OK && rcn_synchronize(ctx_) == RCN_OK && !hipMemcpy(host.data(), i32, nk * 2 * sizeof(int32_t), kMemcpyDeviceToHost) &&
                         !hipMemcpy(host.data() + nk * 2, i32 + 3 * nk, (size_t)n * sizeof(int32_t), kMemcpyDeviceToHost);
@@ -149,7 +171,7 @@ private:
         const size_t c = (size_t)cap;
         if (hipMalloc((void **)&xy_, c * 2 * sizeof(float)) || hipMalloc((void **)&xyInt_, c * 2 * sizeof(int32_t)) || hipMalloc((void **)&size_, c * sizeof(float)) ||
             hipMalloc((void **)&angle_, c * sizeof(float)) || hipMalloc((void **)&resp_, c * sizeof(float)) || hipMalloc((void **)&oct_, c * sizeof(int32_t)) ||
-            hipMalloc((void **)&count_, sizeof(int32_t)) || hipMalloc((void **)&rows_, c * 128 * sizeof(float)))
+            hipMalloc((void **)&count_, sizeof(int32_t)) || hipMalloc((void **)&rows_, c * (size_t)dim_ * sizeof(float)))
             throw std::runtime_error("FeatureClassic: out of device memory");
     }
     void copyOut(void *dst, const void *src, size_t bytes)
@@ -159,7 +181,11 @@ private:
 
     rcn_ctx *ctx_;
     bool owned_;
+    bool orb_;
+    int dim_;
     rcn_sift_options opt_;
+    rcn_orb_options orbOpt_;
+    std::vector<int8_t> orbPattern_;
     int cap_ = 0, runs_ = 0;
     float *xy_ = nullptr, *size_ = nullptr, *angle_ = nullptr, *resp_ = nullptr, *rows_ = nullptr;
     int32_t *xyInt_ = nullptr, *oct_ = nullptr, *count_ = nullptr;
