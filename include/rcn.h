@@ -53,9 +53,10 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_ba_session_loss_report; 11 -> 12 constant cameras and the local adjustment: rcn_ba_solve_constant, rcn_ba_session_solve_local,
  * rcn_ba_session_covisible, rcn_ba_session_local_seconds; 12 -> 13 the homography search rcn_homography_* and the two-view
  * classification rcn_twoview_geometry* with their option structs; 13 -> 14 shared intrinsics: rcn_ba_solve_tied,
- * rcn_ba_session_set_groups).
+ * rcn_ba_session_set_groups; 14 -> 15 the ORB detector rcn_orb_*; 15 -> 16 the binary residency rcn_bits_* and the Hamming matcher
+ * rcn_match_pair_hamming, rcn_match_grid_hamming, rcn_match_grid_hamming_device, rcn_hamming_knn2_device).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 15
+#define RCN_ABI_REVISION 16
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -328,6 +329,44 @@ int rcn_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, flo
  * ctx stream (no host synchronisation inside once the workspace has reached its size).     */
 int rcn_match_grid_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                           int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);
+
+/* ---- matching 256-bit rows under the Hamming distance ------------------------------------------
+ * cv::BFMatcher(NORM_HAMMING).knnMatch(k = 2) behind the same ratio test and uniqueness, for ORB's packed rows (bytes_out_dev of
+ * rcn_orb_describe_device / rcn_orb_detect_and_compute_device).  Everything is integer: d(i, j) = popcount(q_i XOR t_j) in 0 .. 256,
+ * train rows ordered by (d, j) ascending (a tie goes to the lower train row, for the best and the second neighbour), the test
+ * float(d0) < ratio * float(d1) in fp32 (d0 == d1 never passes), the lowest passing query row keeps a contested train row, fewer than two
+ * train rows give no matches.  n_bytes must be 32 (RCN_ERR_ARG otherwise), K at most 32768 rows per image (RCN_ERR_ARG, nothing allocated).
+ *
+ * The binary rows are a residency of their own beside the float descriptors of rcn_desc_*: uploading or clearing one set leaves the other
+ * untouched.  The ids are the same image ids (rcn_coords_upload, the epipolar filter and the match lists apply as they are).
+ *   rcn_bits_upload               K rows of n_bytes from HOST memory as image img_id (replaces it); waits for its copy.
+ *   rcn_bits_upload_batch_device  n_images images of K row slots each from DEVICE memory, bytes_dev [n][K][n_bytes]; image i has
+ *                                 clamp(counts_dev[i], 0, K) rows (counts_dev == NULL: K each; ORB's counts, which may exceed K or be -1,
+ *                                 are taken as they are, on the device: no host round trip).  Rows past that never take part, whatever
+ *                                 bytes they hold.  The rows are copied (expanded to one int8 per bit, 256 bytes per row, resident in the
+ *                                 ctx); asynchronous on the ctx stream.
+ *   rcn_bits_remove / rcn_bits_clear / rcn_bits_count   as rcn_desc_remove / rcn_desc_clear / rcn_desc_count.
+ * rcn_match_pair_hamming: one pair straight from host rows.  rcn_match_grid_hamming / rcn_match_grid_hamming_device: the dense table of
+ * rcn_match_grid / rcn_match_grid_device over the resident binary rows (out[p][i] = train row or -1, the tail up to out_stride -1,
+ * counts[p]; out_stride >= K of every query image; pairs_host == NULL: every i < j over the resident binary ids, n_pairs = n (n - 1) / 2);
+ * rcn_match_compact_begin, rcn_match_table_filter_device and rcn_match_lists_upload take the table unchanged.
+ * rcn_hamming_knn2_device: the two neighbours themselves, knn_dev [n_pairs][stride][4] = (j0, d0, j1, d1) per query row, -1 where
+ * absent (rows past the query image's, a train image with fewer rows); stride >= K of every query image.
+ * The top-2 workspace is chunked over pairs by rcn_match_set_workspace_rows (at most 2^25 row slots per chunk); the result does not
+ * depend on the chunking.  RCN_ERR_NOT_FOUND: an image id without resident binary rows. */
+int rcn_bits_upload(rcn_ctx *ctx, int32_t img_id, const uint8_t *bytes_host, int32_t K, int32_t n_bytes);
+int rcn_bits_upload_batch_device(rcn_ctx *ctx, int32_t first_img_id, int32_t n_images, const uint8_t *bytes_dev /*[n][K][n_bytes]*/,
+                                 const int32_t *counts_dev /*[n], NULL = K each*/, int32_t K, int32_t n_bytes);
+int rcn_bits_remove(rcn_ctx *ctx, int32_t img_id);
+int rcn_bits_clear(rcn_ctx *ctx);
+int rcn_bits_count(const rcn_ctx *ctx);
+int rcn_match_pair_hamming(rcn_ctx *ctx, const uint8_t *q_host, int32_t K1, const uint8_t *t_host, int32_t K2, int32_t n_bytes, float ratio,
+                           int32_t *out_train_for_query /* K1 */, int32_t *out_count);
+int rcn_match_grid_hamming(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
+                           int32_t *out_host, int64_t out_stride, int32_t *counts_host);
+int rcn_match_grid_hamming_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
+                                  int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);
+int rcn_hamming_knn2_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *knn_dev, int64_t stride);
 
 /* ---- host materialisation of a match table ------------------------------------------------
  * The (query feature, train feature) lists the pair loop keeps in featureMatches

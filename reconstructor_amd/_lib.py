@@ -50,6 +50,8 @@ SYMBOLS = [
     "rcn_sift_describe_device", "rcn_sift_detect_and_compute_device",
     "rcn_orb_default_options", "rcn_orb_default_pattern", "rcn_orb_layout", "rcn_orb_set_chunk_images", "rcn_orb_pyramid_device", "rcn_orb_fast_device",
     "rcn_orb_detect_device", "rcn_orb_describe_device", "rcn_orb_detect_and_compute_device",
+    "rcn_bits_upload", "rcn_bits_upload_batch_device", "rcn_bits_remove", "rcn_bits_clear", "rcn_bits_count",
+    "rcn_match_pair_hamming", "rcn_match_grid_hamming", "rcn_match_grid_hamming_device", "rcn_hamming_knn2_device",
     "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
@@ -343,6 +345,23 @@ def load():
     L.rcn_orb_describe_device.argtypes = orb_pyr + [i32, vp, vp, vp, vp, vp]
     L.rcn_orb_detect_and_compute_device.restype = C.c_int
     L.rcn_orb_detect_and_compute_device.argtypes = orb_img + [i32] + sift_kp + [vp, vp]
+    L.rcn_bits_upload.restype = C.c_int
+    L.rcn_bits_upload.argtypes = [vp, i32, vp, i32, i32]
+    L.rcn_bits_upload_batch_device.restype = C.c_int
+    L.rcn_bits_upload_batch_device.argtypes = [vp, i32, i32, vp, vp, i32, i32]
+    L.rcn_bits_remove.restype = C.c_int
+    L.rcn_bits_remove.argtypes = [vp, i32]
+    L.rcn_bits_clear.restype = C.c_int
+    L.rcn_bits_clear.argtypes = [vp]
+    L.rcn_bits_count.restype = C.c_int
+    L.rcn_bits_count.argtypes = [vp]
+    L.rcn_match_pair_hamming.restype = C.c_int
+    L.rcn_match_pair_hamming.argtypes = [vp, vp, i32, vp, i32, i32, f32, vp, C.POINTER(i32)]
+    for fn in (L.rcn_match_grid_hamming, L.rcn_match_grid_hamming_device):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, i32, f32, vp, i64, vp]
+    L.rcn_hamming_knn2_device.restype = C.c_int
+    L.rcn_hamming_knn2_device.argtypes = [vp, vp, i32, vp, i64]
     L.rcn_retr_default_options.restype = None
     L.rcn_retr_default_options.argtypes = [C.POINTER(RetrOptions)]
     L.rcn_retr_codebook_train_device.restype = C.c_int

@@ -157,6 +157,8 @@ struct BaProbe {
     std::vector<double> log;           // per iteration up to the captured one: scal[0 .. 14) as read behind the step, then the number of backtracks
 };
 
+struct HamState;        // hamming.hip: the resident binary rows and the workspace of the Hamming matcher
+
 struct rcn_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -294,6 +296,7 @@ struct rcn_ctx {
     uint64_t ba_graph_serial = 0;
     uint64_t ba_pair_token = 0;         // whose pair lists the Schur-build workspace holds (0 = nobody's)
     std::vector<int> ba_pair_camdim;    // ... and the per-camera tangent dimensions they were built for (a camera without free parameters has no pairs)
+    HamState *ham = nullptr;            // hamming.hip: created by the first rcn_bits_* / Hamming call, released by rcn_int_ham_release
     CholState chol;                     // the dense factorisation of the reduced system (chol.h, chol.hip)
     BaProbe *ba_probe = nullptr;        // tools/ba_step_check.hip only: one LM iteration copied out (above)
     double *ba_host_scal = nullptr;   // pinned mirror of the LM step's scalars (16 doubles; [15]: sequence number), written by the step's last kernel
@@ -350,6 +353,7 @@ int rcn_int_ba_loss_check(rcn_ctx *ctx, const rcn_ba_loss *loss, const char *who
 int rcn_int_ba_loss_report(rcn_ctx *ctx, int no, const double *poses_dev, const double *intr_dev, const double *pts_dev, const double *uv_dev,
                            const int *ocam_dev, const int *opt_dev, const rcn_ba_loss *loss, rcn_ba_loss_report *report, double *weights_host);
 int rcn_match_release(rcn_ctx *ctx);
+void rcn_int_ham_release(rcn_ctx *ctx);      // hamming.hip: the binary residency and its workspace (rcn_destroy)
 // triangulate.hip, with ctx->mu held: the host-side structure check, the workspace size and the launches (all pointers in
 // HBM; compact / n_accepted may be NULL)
 int rcn_int_triangulate_check(rcn_ctx *ctx, int32_t n_cams, int32_t n_tracks, int32_t n_obs, const int32_t *trk_off, const int32_t *obs_cam);

@@ -7,6 +7,8 @@
 //                      holds the 128 floats of the row converted to CV_32F (:24, :30-32)
 //   detectBatch        n images that are in HBM already; the rows stay there, [n][K][128] in a buffer of the caller's (the slot
 //                      of rcn_shard_reserve, for one); only the integer coordinates and the counts come to the host
+//   detectBatchPacked  the ORB branch's batch with the descriptor's 32 BYTES per keypoint and the counts left in HBM, as
+//                      rcn_bits_upload_batch_device takes them (the Hamming matcher, HipFeatureMatcher.h); only the coordinates come back
 //   Detector           the reference's one-line switch (FeatureDetector.cpp:9, :19): Sift (the default, cv::SIFT::create()) or Orb
 //                      (cv::ORB::create() = rcn_orb_detect_and_compute_device): rows of 32 floats, the descriptor's bytes converted
 //                      to CV_32F (:24); setOrbPattern supplies the 256 tests (NULL: the built-in pattern)
@@ -148,6 +150,38 @@ public:
         (void)hipFree(f);
         (void)hipFree(i32);
         if (!ok) throw std::runtime_error(std::string("FeatureClassic::detectBatch: ") + rcn_last_error(ctx_));
+        for (int i = 0; i < n; ++i) {
+            counts[(size_t)i] = host[nk * 2 + (size_t)i];
+            const int m = counts[(size_t)i] < K ? (counts[(size_t)i] < 0 ? 0 : counts[(size_t)i]) : K;
+            for (int k = 0; k < m; ++k) coords[(size_t)i].emplace_back(host[((size_t)i * K + k) * 2], host[((size_t)i * K + k) * 2 + 1]);
+        }
+    }
+    // Detector::Orb only.  bytesOutDev: [n][K][32] bytes in HBM; countsOutDev: [n] int32 in HBM, ORB's own counts (uncapped; -1: a level
+    // overflowed) -- both as rcn_bits_upload_batch_device(ctx, firstId, n, bytesOutDev, countsOutDev, K, 32) takes them, no host round trip
+    // for either.  coords / counts as detectBatch.
+    void detectBatchPacked(const uint8_t *imagesDev, int n, int rows, int cols, int K, uint8_t *bytesOutDev, int32_t *countsOutDev,
+                           std::vector<std::vector<FeatCoord<>>> &coords, std::vector<int> &counts)
+    {
+        if (!orb_) throw std::runtime_error("FeatureClassic::detectBatchPacked: packed rows are the ORB detector's");
+        coords.assign((size_t)(n > 0 ? n : 0), {});
+        counts.assign((size_t)(n > 0 ? n : 0), 0);
+        if (n <= 0) return;
+        if (!bytesOutDev || !countsOutDev) throw std::runtime_error("FeatureClassic::detectBatchPacked: null output");
+        const size_t nk = (size_t)n * K;
+        float *f = nullptr;
+        int32_t *i32 = nullptr;
+        if (hipMalloc((void **)&f, nk * (5 + 32) * sizeof(float)) || hipMalloc((void **)&i32, nk * 3 * sizeof(int32_t))) {
+            if (f) (void)hipFree(f);
+            throw std::runtime_error("FeatureClassic: out of device memory");
+        }
+        const int rc = rcn_orb_detect_and_compute_device(ctx_, imagesDev, RCN_ORB_INPUT_U8, (int64_t)rows * cols, cols, 1, n, rows, cols, &orbOpt_, K, f, i32,
+                                                         f + 2 * nk, f + 3 * nk, f + 4 * nk, i32 + 2 * nk, countsOutDev, f + 5 * nk, bytesOutDev);
+        std::vector<int32_t> host(nk * 2 + (size_t)n);
+        const bool ok = rc == RCN_OK && rcn_synchronize(ctx_) == RCN_OK && !hipMemcpy(host.data(), i32, nk * 2 * sizeof(int32_t), kMemcpyDeviceToHost) &&
+                        !hipMemcpy(host.data() + nk * 2, countsOutDev, (size_t)n * sizeof(int32_t), kMemcpyDeviceToHost);
+        (void)hipFree(f);
+        (void)hipFree(i32);
+        if (!ok) throw std::runtime_error(std::string("FeatureClassic::detectBatchPacked: ") + rcn_last_error(ctx_));
         for (int i = 0; i < n; ++i) {
             counts[(size_t)i] = host[nk * 2 + (size_t)i];
             const int m = counts[(size_t)i] < K ? (counts[(size_t)i] < 0 ? 0 : counts[(size_t)i]) : K;

@@ -18,6 +18,10 @@
 // the plugin's own range; a pair call then is one rcn_match_grid over two resident ids.  Least recently used images
 // are replaced beyond `capacity` images.  Descriptors are written once by the detector and never edited afterwards
 // in the reference; a caller that edits rows IN PLACE (same storage, rows outside the sample) MUST call invalidate().
+//
+// `HipHammingMatcher` is the matcher of the ORB branch: cv::BFMatcher(NORM_HAMMING) behind the same ratio test and uniqueness loop.
+// The 32 floats of a row are packed back into the descriptor's bytes (packBinaryRows, PackBinaryRows.h) and go through
+// rcn_match_pair_hamming; a row that is not 32 integers in 0 .. 255 is not a binary descriptor and throws std::invalid_argument.
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -27,6 +31,7 @@
 #include <string>
 
 #include "../../include/rcn.h"
+#include "PackBinaryRows.h"
 #include "rcn_types.h"
 
 namespace reconstructor::Core {
@@ -194,6 +199,55 @@ private:
     size_t capacity_ = 64;
     std::atomic<size_t> uploads_{0};
     uint64_t clock_ = 0;
+    const float ratioThresh = 0.7;   // FeatureMatcher.h:45
+};
+
+// K x 32 bytes of an image whose featDesc rows hold one float per descriptor byte
+inline std::vector<uint8_t> packBinaryRows(const std::vector<FeaturePtr<>> &features)
+{
+    std::vector<uint8_t> out(features.size() * kBinaryRowBytes);
+    for (size_t i = 0; i < features.size(); ++i) {
+        const std::vector<float> &d = features[i]->featDesc.desc;
+        packBinaryRow(d.data(), d.size(), out.data() + i * kBinaryRowBytes);
+    }
+    return out;
+}
+
+class HipHammingMatcher : public FeatureMatcher {
+public:
+    explicit HipHammingMatcher(int device = 0) : owned_(true)
+    {
+        if (rcn_create(device, &ctx_) != RCN_OK) throw std::runtime_error("HipHammingMatcher: no usable gfx950 device");
+    }
+    explicit HipHammingMatcher(rcn_ctx *shared) : ctx_(shared), owned_(false)
+    {
+        if (!ctx_) throw std::runtime_error("HipHammingMatcher: null ctx");
+    }
+    ~HipHammingMatcher() override { if (owned_) rcn_destroy(ctx_); }
+    HipHammingMatcher(const HipHammingMatcher &) = delete;
+    HipHammingMatcher &operator=(const HipHammingMatcher &) = delete;
+
+    void matchFeatures(const std::vector<FeaturePtr<>> &features1,
+                       const std::vector<FeaturePtr<>> &features2, std::map<int, int> &matches,
+                       const std::pair<int, int> /*imgShape1*/, const std::pair<int, int> /*imgShape2*/) override
+    {
+        if (features1.empty() || features2.empty()) return;   // the reference asserts here (:39)
+        const std::vector<uint8_t> q = packBinaryRows(features1), t = packBinaryRows(features2);
+        std::vector<int32_t> out(features1.size(), -1);
+        int32_t count = 0;
+        std::lock_guard<std::mutex> lk(mu_);
+        const int rc = rcn_match_pair_hamming(ctx_, q.data(), (int32_t)features1.size(), t.data(), (int32_t)features2.size(), (int32_t)kBinaryRowBytes,
+                                              ratioThresh, out.data(), &count);
+        if (rc != RCN_OK) throw std::runtime_error(std::string("HipHammingMatcher::matchFeatures: ") + rcn_last_error(ctx_));
+        for (size_t i = 0; i < out.size(); ++i)
+            if (out[i] >= 0) matches[(int)i] = out[i];
+    }
+    rcn_ctx *context() { return ctx_; }
+
+private:
+    rcn_ctx *ctx_ = nullptr;
+    bool owned_ = true;
+    std::mutex mu_;
     const float ratioThresh = 0.7;   // FeatureMatcher.h:45
 };
 
