@@ -54,9 +54,11 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_ba_session_covisible, rcn_ba_session_local_seconds; 12 -> 13 the homography search rcn_homography_* and the two-view
  * classification rcn_twoview_geometry* with their option structs; 13 -> 14 shared intrinsics: rcn_ba_solve_tied,
  * rcn_ba_session_set_groups; 14 -> 15 the ORB detector rcn_orb_*; 15 -> 16 the binary residency rcn_bits_* and the Hamming matcher
- * rcn_match_pair_hamming, rcn_match_grid_hamming, rcn_match_grid_hamming_device, rcn_hamming_knn2_device).
+ * rcn_match_pair_hamming, rcn_match_grid_hamming, rcn_match_grid_hamming_device, rcn_hamming_knn2_device; 16 -> 17 guided matching
+ * rcn_match_guided*, rcn_match_pair_guided, rcn_guided_knn2_device, rcn_match_grid_guided with rcn_guided_options, and
+ * rcn_match_table_filter_model_device).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 16
+#define RCN_ABI_REVISION 17
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -1137,6 +1139,49 @@ int rcn_coords_clear(rcn_ctx *ctx);
  * small host-to-device copy. */
 int rcn_match_table_filter_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
                                   int64_t stride, int32_t *counts_dev, int32_t *out_status_dev);
+
+/* The same filter, keeping every pair's model: out_F_dev [n_pairs][9] doubles, row-major, the winning 7-point hypothesis as
+ * rcn_fmat_filter_grid_device's out_F_dev writes it on the same lists, zeros for a pair without one (fewer than 7 matches, or no model
+ * found).  Table, counts and status are those of rcn_match_table_filter_device bit for bit. */
+int rcn_match_table_filter_model_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
+                                        int64_t stride, int32_t *counts_dev, int32_t *out_status_dev, double *out_F_dev);
+
+/* ---- guided matching: the exact 2-NN inside the epipolar band of each pair ----------------------
+ * For pair (i, j) and its model F (9 doubles, row-major, the filter's convention: p1 the query point of image i, p2 the train
+ * point of image j, residual p2^T F p1) a train row is a CANDIDATE of a query row when both points lie within max_error_px of the
+ * other's epipolar line -- csrc/guided_band.h, division-free fp64 on the resident integer coordinates; a zero, non-finite or
+ * degenerate F has no candidates.  Among a row's candidates only, distance and order are the matcher's own (canonical fp64 chain,
+ * ascending (d2, train row), dist = sqrtf((float)d2)).  A row is accepted when dist0 < ratio * dist1 in fp32 (dist1 = +inf for a lone
+ * candidate) and, with max_distance > 0, dist0 <= max_distance.  cross_check == 0: the lowest query row keeps a contested train row;
+ * cross_check != 0: a match must also be the accepted choice of its train row in the reversed pair under F^T (the band is the exact
+ * transpose, d2 symmetric in its bits), so no train row appears twice.
+ * Needs the fp32 descriptors (rcn_desc_*) and the coordinates (rcn_coords_upload*) of every image named, with equal counts.
+ * Errors: NOT_FOUND for an image without either, ARG for unequal counts, a stride below a query image's K, a ratio or max_error_px that
+ * is not finite-positive (max_error_px = +inf is allowed: every pair of rows is in the band of a non-degenerate F), null pointers. */
+typedef struct { float ratio; float max_error_px; float max_distance; int32_t cross_check; } rcn_guided_options;
+int rcn_guided_default_options(rcn_guided_options *o);      /* 0.7f, 3.0f, 0 (off), 0 */
+/* out_dev [n_pairs][out_stride]: train row per query row or -1, the tail of each row -1; counts_dev [n_pairs]: entries >= 0;
+ * cand_dev (may be NULL) [n_pairs]: in-band (query, train) combinations of the pair.  Pairs run in chunks under
+ * rcn_match_set_workspace_rows (4 bytes per train row of a chunk; no K1 x K2 array exists); the result does not depend on the chunking.
+ * Asynchronous on the ctx stream after one small host-to-device copy. */
+int rcn_match_guided_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, const double *F_dev, const rcn_guided_options *opt,
+                            int32_t *out_dev, int64_t out_stride, int32_t *counts_dev, int64_t *cand_dev);
+/* The same with F, out, counts and cand (may be NULL) on the HOST. */
+int rcn_match_guided(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, const double *F_host, const rcn_guided_options *opt,
+                     int32_t *out_host, int64_t out_stride, int32_t *counts_host, int64_t *cand_host);
+/* One pair straight from host rows and coordinates (nothing resident is touched). */
+int rcn_match_pair_guided(rcn_ctx *ctx, const float *q_host, int32_t K1, const int32_t *xy1_host, const float *t_host, int32_t K2,
+                          const int32_t *xy2_host, int32_t D, const double *F, const rcn_guided_options *opt,
+                          int32_t *out_train_for_query, int32_t *out_count);
+/* The two neighbours themselves: idx_dev [n_pairs][stride][4] = (j0, j1, candidates of the row, 0), -1 where absent; d2_dev
+ * [n_pairs][stride][2] = their squared distances, +inf where absent.  Rows past a query image's K: (-1, -1, 0, 0) and +inf. */
+int rcn_guided_knn2_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, const double *F_dev, float max_error_px,
+                           int32_t *idx_dev, double *d2_dev, int64_t stride);
+/* The body of the pair loop with the guided step, results on the HOST: rcn_match_grid_device, rcn_match_table_filter_model_device, then
+ * rcn_match_guided_device (opt; opt->ratio is the guided step's ratio, `ratio` the first match's) on every pair whose verdict is > 0;
+ * the other pairs keep the filtered table.  status_host (may be NULL): the filter's verdict per pair. */
+int rcn_match_grid_guided(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio, const rcn_guided_options *opt,
+                          int32_t *out_host, int64_t out_stride, int32_t *counts_host, int32_t *status_host);
 
 /* The body of the pair loop (:232-275) for a list of pairs over resident images, results on the HOST: match, then --
  * filter != 0 -- the filter above on the table where it lies in HBM, then the dense table (as rcn_match_grid), the

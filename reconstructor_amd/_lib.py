@@ -52,6 +52,8 @@ SYMBOLS = [
     "rcn_orb_detect_device", "rcn_orb_describe_device", "rcn_orb_detect_and_compute_device",
     "rcn_bits_upload", "rcn_bits_upload_batch_device", "rcn_bits_remove", "rcn_bits_clear", "rcn_bits_count",
     "rcn_match_pair_hamming", "rcn_match_grid_hamming", "rcn_match_grid_hamming_device", "rcn_hamming_knn2_device",
+    "rcn_guided_default_options", "rcn_match_guided_device", "rcn_match_guided", "rcn_match_pair_guided", "rcn_guided_knn2_device",
+    "rcn_match_table_filter_model_device", "rcn_match_grid_guided",
     "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
@@ -162,6 +164,10 @@ class OrbLayout(C.Structure):
 
 class ImgOptions(C.Structure):
     _fields_ = [("order", C.c_int32), ("gray_bits", C.c_int32)]
+
+
+class GuidedOptions(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("max_error_px", C.c_float), ("max_distance", C.c_float), ("cross_check", C.c_int32)]
 
 
 class RetrOptions(C.Structure):
@@ -362,6 +368,19 @@ def load():
         fn.argtypes = [vp, vp, i32, f32, vp, i64, vp]
     L.rcn_hamming_knn2_device.restype = C.c_int
     L.rcn_hamming_knn2_device.argtypes = [vp, vp, i32, vp, i64]
+    L.rcn_guided_default_options.restype = C.c_int
+    L.rcn_guided_default_options.argtypes = [C.POINTER(GuidedOptions)]
+    for fn in (L.rcn_match_guided_device, L.rcn_match_guided):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, i32, vp, C.POINTER(GuidedOptions), vp, i64, vp, vp]
+    L.rcn_match_pair_guided.restype = C.c_int
+    L.rcn_match_pair_guided.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, C.POINTER(GuidedOptions), vp, C.POINTER(i32)]
+    L.rcn_guided_knn2_device.restype = C.c_int
+    L.rcn_guided_knn2_device.argtypes = [vp, vp, i32, vp, f32, vp, vp, i64]
+    L.rcn_match_table_filter_model_device.restype = C.c_int
+    L.rcn_match_table_filter_model_device.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp]
+    L.rcn_match_grid_guided.restype = C.c_int
+    L.rcn_match_grid_guided.argtypes = [vp, vp, i32, f32, C.POINTER(GuidedOptions), vp, i64, vp, vp]
     L.rcn_retr_default_options.restype = None
     L.rcn_retr_default_options.argtypes = [C.POINTER(RetrOptions)]
     L.rcn_retr_codebook_train_device.restype = C.c_int

@@ -803,9 +803,19 @@ extern "C" int rcn_match_table_filter_device(rcn_ctx *ctx, const int32_t *pairs_
     return rcn_int_table_filter(ctx, pairs_host, n_pairs, table_dev, stride, counts_dev, out_status_dev);
 }
 
-// the same with ctx->mu held by the caller (shard.hip, rcn_match_grid_filtered)
+// the same filter, keeping each pair's model for the guided matcher (guided.hip): out_F_dev [n_pairs][9], zeros where there is none
+extern "C" int rcn_match_table_filter_model_device(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
+                                                   int64_t stride, int32_t *counts_dev, int32_t *out_status_dev, double *out_F_dev)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (n_pairs > 0 && !out_F_dev) { ctx->set_error("rcn_match_table_filter_model_device: null model output"); return RCN_ERR_ARG; }
+    return rcn_int_table_filter(ctx, pairs_host, n_pairs, table_dev, stride, counts_dev, out_status_dev, out_F_dev);
+}
+
+// the same with ctx->mu held by the caller (shard.hip, rcn_match_grid_filtered, guided.hip); out_F_dev may be NULL
 int rcn_int_table_filter(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
-                         int64_t stride, int32_t *counts_dev, int32_t *out_status_dev)
+                         int64_t stride, int32_t *counts_dev, int32_t *out_status_dev, double *out_F_dev)
 {
     if (n_pairs < 0 || (n_pairs > 0 && (!pairs_host || !table_dev || !counts_dev)) || stride < 0) {
         ctx->set_error("rcn_match_table_filter_device: bad argument");
@@ -849,7 +859,7 @@ int rcn_int_table_filter(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pair
     k_tf_scan<<<1, 1024, 0, st>>>(counts_dev, n_pairs, d_off);
     k_tf_fill<<<n_pairs, 256, 0, st>>>(d_px, table_dev, stride, d_off, d_1, d_2);
     RCN_HIP(hipGetLastError());
-    int rc = fmat_launch(ctx, n_pairs, d_off, d_1, d_2, d_mask, d_ver, d_it, nullptr);
+    int rc = fmat_launch(ctx, n_pairs, d_off, d_1, d_2, d_mask, d_ver, d_it, out_F_dev);
     if (rc) return rc;
     k_tf_apply<<<n_pairs, 256, 0, st>>>(d_px, table_dev, stride, d_off, d_mask, d_ver, counts_dev);
     RCN_HIP(hipGetLastError());

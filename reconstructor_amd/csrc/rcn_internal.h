@@ -265,6 +265,8 @@ struct rcn_ctx {
     DevBuf fm_ws, fm_state;    // epipolar filter (fmat.hip): host-API staging, per-pair RANSAC state
     std::vector<PairXY> fm_pairs_host;   // staging of fm_pairs (uploaded asynchronously)
     DevBuf fm_csr, fm_pairs;   // fused table filter: CSR of the matched points, per-pair coordinate pointers
+    DevBuf gd_pairs, gd_ws, gd_hws, gd_F;   // guided matcher (guided.hip): per-pair pointers, owner / reverse rows of one chunk, host-API staging, the grid's models
+    std::vector<char> gd_pairs_host;        // staging of gd_pairs (uploaded asynchronously)
     std::map<int32_t, std::pair<DevBuf, int32_t>> coords;   // image id -> (K x 2 int32 pixel coordinates in HBM, K)
     CorrLists corr;                     // corr2d3d.hip: resident match lists
     DevBuf corr_ws, corr_hws, corr_slots, att_ws;   // ... workspace (obs_of, hit rows, tile counts), host-API staging, slot table, attach staging
@@ -398,9 +400,10 @@ int rcn_int_compact_begin(rcn_ctx *ctx, const int32_t *table_dev, int64_t stride
 int rcn_int_compact_wait(rcn_ctx *ctx);
 // store.hip: the ordered compaction kernel alone (rcn_shard_gather_lists: the lists stay in HBM)
 void rcn_int_launch_cmp_fill(hipStream_t st, const int32_t *table_dev, int64_t stride, const int32_t *counts_dev, const long long *off, int32_t n_pairs, int2 *qt);
-// fmat.hip: rcn_match_table_filter_device with ctx->mu already held
+// fmat.hip: rcn_match_table_filter_device with ctx->mu already held; out_F_dev (may be NULL): the model of every pair, 9 doubles, zeros
+// where there is none (rcn_match_table_filter_model_device)
 int rcn_int_table_filter(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, int32_t *table_dev,
-                         int64_t stride, int32_t *counts_dev, int32_t *out_status_dev);
+                         int64_t stride, int32_t *counts_dev, int32_t *out_status_dev, double *out_F_dev = nullptr);
 // superglue.hip: rcn_sg_match_device with ctx->mu already held (rcn_sg_net_match_device, superglue_gnn.hip); check_only: the
 // argument checks alone, nothing launched and the descriptor pointers not looked at
 int rcn_int_sg_match(rcn_ctx *ctx, const char *who, const float *d0_dev, int64_t stride_pair0, int64_t stride_row0, int64_t stride_d0,
@@ -427,3 +430,4 @@ int rcn_int_i8_commit(rcn_ctx *ctx);         // int8 path: the residual / quanti
 int rcn_int_resolve_scale(rcn_ctx *ctx);     // host copies of scale / bias / max_norm are current afterwards (may synchronise)
 int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                        int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);
+void rcn_int_guided_release(rcn_ctx *ctx);   // guided.hip: the guided matcher's buffers (rcn_destroy)
