@@ -56,9 +56,9 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_ba_session_set_groups; 14 -> 15 the ORB detector rcn_orb_*; 15 -> 16 the binary residency rcn_bits_* and the Hamming matcher
  * rcn_match_pair_hamming, rcn_match_grid_hamming, rcn_match_grid_hamming_device, rcn_hamming_knn2_device; 16 -> 17 guided matching
  * rcn_match_guided*, rcn_match_pair_guided, rcn_guided_knn2_device, rcn_match_grid_guided with rcn_guided_options, and
- * rcn_match_table_filter_model_device).
+ * rcn_match_table_filter_model_device); 17 -> 18 track building rcn_tracks_* with rcn_tracks_options).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 17
+#define RCN_ABI_REVISION 18
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -1466,6 +1466,55 @@ int  rcn_orb_detect_and_compute_device(rcn_ctx *ctx, const void *images_dev, int
                                        int64_t stride_x, int32_t n, int32_t H, int32_t W, const rcn_orb_options *opt, int32_t K,
                                        float *xy_dev, int32_t *xy_int_dev, float *size_dev, float *angle_dev, float *response_dev,
                                        int32_t *octave_dev, int32_t *counts_dev, float *rows_out_dev, uint8_t *bytes_out_dev);
+
+/* ---- track building (tracks.hip) -----------------------------------------------------------------------
+ * The tracks that the resident match lists (rcn_match_lists_upload) tie together across all their images, as OpenMVG's
+ * TracksBuilder computes them, restated in tests/tracks_ref.py; pure integer set arithmetic, every output bit for bit.
+ *   nodes       one per (image, feature): every image of the resident lists, feature 0 .. K - 1 of its resident coordinates
+ *   edges       every entry (f, g) of every uploaded list (a, b) joins (a, f) and (b, g); `mirror` adds nothing
+ *   conflict    a connected component in which an image occurs with two or more features: RCN_TRACKS_CONFLICT_DROP_TRACK drops the
+ *               component, RCN_TRACKS_CONFLICT_DROP_IMAGE every observation of such an image in it
+ *   selection   n_sel > 0: observations of images outside sel_img are dropped AFTER the conflict rule (an unselected image still
+ *               ties tracks together and still conflicts); sel_cam[k] is the camera row of sel_img[k]
+ *   length      a track is kept when min_length <= n and (max_length == 0 or n <= max_length), n the surviving observations
+ *   order       observations ascend by (image id, feature), tracks by their first surviving observation
+ * Node index: the list images ascending by id, node_off[i] + feature (rcn_tracks_layout, host only: img_ids_out n_images entries,
+ * node_off_out n_images + 1; either may be NULL to ask for *n_images_out alone).
+ *
+ * rcn_tracks_build_device: asynchronous on the ctx stream behind one small staged host-to-device copy (the slot / selection table);
+ * no host synchronisation inside.  counts_dev[0 .. 1]: tracks and observations of the FULL result, also beyond the capacities.
+ * Only whole tracks are written: track j iff tracks 0 .. j fit both capacities; trk_off_dev has cap_tracks + 1 entries, the ones
+ * past the last written track repeat its end (rcn_new_view_tracks_device's convention: rcn_triangulate_device can run over all
+ * cap_tracks rows).  obs_img_dev / obs_feat_dev [cap_obs]; obs_cam_dev [cap_obs] (may be NULL, must be NULL when n_sel == 0);
+ * obs_xy_dev [cap_obs][2] (may be NULL): the resident pixels; feat_track_dev (may be NULL): one int32 per node, the WRITTEN
+ * track's index or -1; stats_dev (may be NULL) int64[8]: components of at least 2 nodes, components with a conflict,
+ * observations dropped by the conflict rule, components of at least 2 nodes (not dropped whole by the conflict rule) that the
+ * length filter dropped, the largest component's nodes, the longest kept track, the edges read, 0.
+ * rcn_tracks_build: the same with host arrays, synchronous; too small a capacity is RCN_ERR_ARG with counts_out set.
+ * RCN_ERR_ARG (with a message): no resident lists, coordinates changed since the lists' upload, a repeated selected image, a negative
+ * camera row, more than 2^31 - 1 nodes, bad options (min_length < 2, max_length < 0 or in 1 .. min_length - 1, an unknown policy, a
+ * non-zero reserved word), a negative capacity, a null required pointer.  RCN_ERR_NOT_FOUND: a selected image that is not among
+ * the list images.  opt == NULL: the defaults. */
+#define RCN_TRACKS_CONFLICT_DROP_TRACK 0
+#define RCN_TRACKS_CONFLICT_DROP_IMAGE 1
+typedef struct {
+    int32_t min_length;                  /* 2, >= 2 */
+    int32_t max_length;                  /* 0: no limit */
+    int32_t conflict;                    /* RCN_TRACKS_CONFLICT_DROP_TRACK */
+    int32_t reserved;                    /* 0 */
+} rcn_tracks_options;
+void rcn_tracks_default_options(rcn_tracks_options *opt);
+int  rcn_tracks_layout(rcn_ctx *ctx, int32_t *img_ids_out, int64_t *node_off_out, int32_t *n_images_out);
+int  rcn_tracks_build_device(rcn_ctx *ctx, const rcn_tracks_options *opt, int32_t n_sel, const int32_t *sel_img_host,
+                             const int32_t *sel_cam_host, int32_t cap_tracks, int32_t cap_obs, int32_t *counts_dev,
+                             int32_t *trk_off_dev, int32_t *obs_img_dev, int32_t *obs_feat_dev, int32_t *obs_cam_dev,
+                             int32_t *obs_xy_dev, int32_t *feat_track_dev, int64_t *stats_dev);
+int  rcn_tracks_build(rcn_ctx *ctx, const rcn_tracks_options *opt, int32_t n_sel, const int32_t *sel_img, const int32_t *sel_cam,
+                      int32_t cap_tracks, int32_t cap_obs, int32_t *counts_out, int32_t *trk_off_out, int32_t *obs_img_out,
+                      int32_t *obs_feat_out, int32_t *obs_cam_out, int32_t *obs_xy_out, int32_t *feat_track_out, int64_t *stats_out);
+/* Milliseconds the six phases of the last rcn_tracks_build* of this ctx took on the device (hook, flatten, conflicts, scans,
+ * scatter, sort); waits for them.  RCN_ERR_ARG before the first build. */
+int  rcn_tracks_last_phase_ms(rcn_ctx *ctx, double *ms_out6);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ SYMBOLS = [
     "rcn_match_pair_hamming", "rcn_match_grid_hamming", "rcn_match_grid_hamming_device", "rcn_hamming_knn2_device",
     "rcn_guided_default_options", "rcn_match_guided_device", "rcn_match_guided", "rcn_match_pair_guided", "rcn_guided_knn2_device",
     "rcn_match_table_filter_model_device", "rcn_match_grid_guided",
+    "rcn_tracks_default_options", "rcn_tracks_layout", "rcn_tracks_build_device", "rcn_tracks_build", "rcn_tracks_last_phase_ms",
     "rcn_retr_default_options", "rcn_retr_codebook_train_device", "rcn_retr_codebook_create", "rcn_retr_codebook_read", "rcn_retr_codebook_destroy",
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
@@ -168,6 +169,10 @@ class ImgOptions(C.Structure):
 
 class GuidedOptions(C.Structure):
     _fields_ = [("ratio", C.c_float), ("max_error_px", C.c_float), ("max_distance", C.c_float), ("cross_check", C.c_int32)]
+
+
+class TracksOptions(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("max_length", C.c_int32), ("conflict", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RetrOptions(C.Structure):
@@ -381,6 +386,15 @@ def load():
     L.rcn_match_table_filter_model_device.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp]
     L.rcn_match_grid_guided.restype = C.c_int
     L.rcn_match_grid_guided.argtypes = [vp, vp, i32, f32, C.POINTER(GuidedOptions), vp, i64, vp, vp]
+    L.rcn_tracks_default_options.restype = None
+    L.rcn_tracks_default_options.argtypes = [C.POINTER(TracksOptions)]
+    L.rcn_tracks_layout.restype = C.c_int
+    L.rcn_tracks_layout.argtypes = [vp, vp, vp, C.POINTER(i32)]
+    for fn in (L.rcn_tracks_build_device, L.rcn_tracks_build):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.POINTER(TracksOptions), i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rcn_tracks_last_phase_ms.restype = C.c_int
+    L.rcn_tracks_last_phase_ms.argtypes = [vp, vp]
     L.rcn_retr_default_options.restype = None
     L.rcn_retr_default_options.argtypes = [C.POINTER(RetrOptions)]
     L.rcn_retr_codebook_train_device.restype = C.c_int

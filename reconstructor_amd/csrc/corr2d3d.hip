@@ -886,6 +886,9 @@ int rcn_match_lists_upload(rcn_ctx *ctx, int32_t n_pairs, const int32_t *pairs, 
     L.id_lo = lo;
     L.id_span = (int32_t)span;
     L.mirror = mirror != 0;
+    L.n_pairs = n_pairs;
+    L.n_ent = n_ent;
+    L.coords_gen = ctx->coords_gen;
     L.live = true;
     if (!ctx->corr_ev && hipEventCreateWithFlags(&ctx->corr_ev, hipEventDisableTiming) != hipSuccess) { ctx->corr_ev = nullptr; RCN_HIP(hipGetLastError()); }
     return RCN_OK;

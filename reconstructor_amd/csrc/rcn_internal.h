@@ -129,6 +129,9 @@ struct CorrLists {
     DevBuf list_off;                  // int64, n_pairs + 1
     DevBuf dir;                       // n_slots x n_slots int32: (list << 1) | read backwards (mirror), -1 = no list
     DevBuf id2slot;                   // int32, -1 = not in the lists
+    int32_t n_pairs = 0;              // lists uploaded
+    int64_t n_ent = 0;                // their entries
+    uint64_t coords_gen = 0;          // ctx->coords_gen at the upload: the entries were checked against those row counts
     void release() { ent.release(); list_off.release(); dir.release(); id2slot.release(); ids.clear(); live = false; id_lo = id_span = 0; }
 };
 
@@ -298,6 +301,14 @@ struct rcn_ctx {
     uint64_t ba_graph_serial = 0;
     uint64_t ba_pair_token = 0;         // whose pair lists the Schur-build workspace holds (0 = nobody's)
     std::vector<int> ba_pair_camdim;    // ... and the per-camera tangent dimensions they were built for (a camera without free parameters has no pairs)
+    // track building (tracks.hip): workspace, the slot / selection table and its staging (uploaded asynchronously; trk_ev marks the copy),
+    // the events around the six phases of the last build
+    DevBuf trk_ws, trk_slots, trk_hws;
+    std::vector<char> trk_stage_host;
+    hipEvent_t trk_ev = nullptr;
+    bool trk_stage_pending = false;
+    hipEvent_t trk_tev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool trk_timed = false;
     HamState *ham = nullptr;            // hamming.hip: created by the first rcn_bits_* / Hamming call, released by rcn_int_ham_release
     CholState chol;                     // the dense factorisation of the reduced system (chol.h, chol.hip)
     BaProbe *ba_probe = nullptr;        // tools/ba_step_check.hip only: one LM iteration copied out (above)
@@ -430,4 +441,5 @@ int rcn_int_i8_commit(rcn_ctx *ctx);         // int8 path: the residual / quanti
 int rcn_int_resolve_scale(rcn_ctx *ctx);     // host copies of scale / bias / max_norm are current afterwards (may synchronise)
 int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                        int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);
+void rcn_int_tracks_release(rcn_ctx *ctx);   // tracks.hip: the track builder's buffers and events (rcn_destroy)
 void rcn_int_guided_release(rcn_ctx *ctx);   // guided.hip: the guided matcher's buffers (rcn_destroy)
