@@ -56,9 +56,11 @@ const char *rcn_last_error(const rcn_ctx *ctx);      /* never NULL */
  * rcn_ba_session_set_groups; 14 -> 15 the ORB detector rcn_orb_*; 15 -> 16 the binary residency rcn_bits_* and the Hamming matcher
  * rcn_match_pair_hamming, rcn_match_grid_hamming, rcn_match_grid_hamming_device, rcn_hamming_knn2_device; 16 -> 17 guided matching
  * rcn_match_guided*, rcn_match_pair_guided, rcn_guided_knn2_device, rcn_match_grid_guided with rcn_guided_options, and
- * rcn_match_table_filter_model_device); 17 -> 18 track building rcn_tracks_* with rcn_tracks_options).
+ * rcn_match_table_filter_model_device); 17 -> 18 track building rcn_tracks_* with rcn_tracks_options;
+ * 18 -> 19 the plane sweep rcn_mvs_* with rcn_mvs_options and rcn_mvs_sizes, rcn_img_undistort_device
+ * and rcn_ba_session_mvs_views).
  * rcn_version() names the library build ("reconstructor_amd 0.<revision> (gfx950)"); compare the two at start-up. */
-#define RCN_ABI_REVISION 18
+#define RCN_ABI_REVISION 19
 const char *rcn_version(void);
 /* Run all work of this ctx on an existing HIP stream (e.g. torch's current stream, passed as
  * the raw hipStream_t).  NULL = the ctx's own stream.  */
@@ -1515,6 +1517,73 @@ int  rcn_tracks_build(rcn_ctx *ctx, const rcn_tracks_options *opt, int32_t n_sel
 /* Milliseconds the six phases of the last rcn_tracks_build* of this ctx took on the device (hook, flatten, conflicts, scans,
  * scatter, sort); waits for them.  RCN_ERR_ARG before the first build. */
 int  rcn_tracks_last_phase_ms(rcn_ctx *ctx, double *ms_out6);
+
+/* ---- plane-sweep depth maps, the cross-view check and the dense cloud ----------------------------------
+ * The adjusted cameras and the prepared photographs -> per-view depth maps and a dense coloured cloud: the classical
+ * fronto-parallel plane sweep with a ZNCC cost, a winner-takes-all depth, a consistency check against the source views' own
+ * maps and a direct fusion.  Defined by tests/mvs_ref.py; every output array equals it bit for bit (integer window sums, each
+ * floating-point step one separately rounded double in the order of csrc/mvs_geom.h).
+ *
+ * Cameras: poses34 rows of [R | t] (world -> camera) and intrinsics rows of six (fx fy cx cy k1 k2), as the BA session holds
+ * them.  The sweep is pinhole; rcn_img_undistort_device removes k1, k2 beforehand: out[y][x] = the 5-bit bilinear sample of
+ * the distorted plane at (fx (xn + d) + cx, fy (yn + d) + cy), xn = (x - cx) / fx, d = k1 rho + (k2 rho) rho, rho = xn^2 + yn^2,
+ * rounded by (v + 512) >> 10, 0 outside; the identity when k1 = k2 = 0.  out: dense [n][rows][cols][channels].
+ *
+ * Planes: per reference view a list inv[D] of inverse depths (any order, repeats allowed; rcn_mvs_inv_depths: uniform in
+ * inverse depth from 1 / far up to 1 / near, the middle when D == 1).  rcn_mvs_homographies (pure host code, no contraction):
+ * H_out[s][k] = K_s (R_rel + t_rel e3^T inv[k]) K_r^-1 row-major, zeros for a source < 0.
+ *
+ * Views: views_host [V][1 + S] = (reference image, S source images, -1: none).  rcn_mvs_sweep_device: one launch for the V
+ * views; a view's bits do not depend on the batch.  plane_out int16 (-1: invalid), depth_out float (0: invalid), cost_out
+ * float (+inf: invalid), each dense [V][rows][cols].  rcn_mvs_consistency_device: mask_out uint8 [V][rows][cols], counts_out
+ * int32 [V]; a source that is no reference view of the batch agrees with nothing.  rcn_mvs_fuse_device: the kept pixels of
+ * every stride-th row and column as rcn_cloud_write_ply's 16-byte records in (view, y, x) order; only whole rows are written:
+ * row j iff rows 0 .. j fit `capacity`; counts_out_dev int64[2] = (vertices written, vertices of the full result).  rgb_dev
+ * [n][rows][cols][3] may be NULL (black).  All three are asynchronous on the ctx stream behind one small staged copy of the
+ * view table.  opt == NULL: the defaults.
+ * RCN_ERR_ARG (with a message): a null required pointer, radius outside 1 .. 5, D outside 1 .. 1024, S outside 1 .. 16, a
+ * reference listed as its own source, an image index outside the batch, a non-positive size, rows * cols > 2^29 - 1, more than
+ * 65535 views or 2^24 - 1 tiles / sampled rows in one launch, a bad option.  V == 0 launches nothing. */
+#define RCN_MVS_MAX_PLANES 1024
+#define RCN_MVS_MAX_SOURCES 16
+typedef struct {
+    int32_t radius;                      /* 3: the ZNCC window is (2 radius + 1)^2, 1 .. 5 */
+    int32_t min_sources;                 /* 2: a plane's cost is +inf with fewer valid sources */
+    int32_t min_consistent;              /* 2: sources that must agree with a pixel's depth */
+    int32_t stride;                      /* 1: the fusion takes every stride-th row and column */
+    double max_cost;                     /* 0.5: a pixel whose best cost exceeds it is invalid */
+    double rel_tol;                      /* 0.01: |z_s - z'_s| <= rel_tol z_s */
+} rcn_mvs_options;
+typedef struct {
+    int32_t tile, tiles_x, tiles_y;      /* the sweep's tile edge and tiles per view */
+    int32_t lds_bytes;                   /* LDS of one workgroup of k_mvs_sweep */
+    int64_t pixels;                      /* V rows cols: elements of plane / depth / cost / mask */
+    int64_t h_doubles;                   /* V S D 9: doubles of the homography table */
+    int64_t samples;                     /* pixels D S: warped samples of a full sweep */
+} rcn_mvs_sizes;
+void rcn_mvs_default_options(rcn_mvs_options *opt);
+int  rcn_mvs_layout(int32_t rows, int32_t cols, int32_t V, int32_t D, int32_t S, int32_t radius, rcn_mvs_sizes *out);
+int  rcn_mvs_inv_depths(double near_z, double far_z, int32_t D, double *inv_out);
+int  rcn_mvs_homographies(const double *poses34, const double *intrinsics, int32_t ref, const int32_t *srcs, int32_t S, const double *inv, int32_t D,
+                          double *H_out /*[S][D][9]*/);
+int  rcn_img_undistort_device(rcn_ctx *ctx, const uint8_t *src_dev, int64_t stride_img_bytes, int64_t stride_row_bytes, int32_t channels /*1 | 3*/, int32_t n,
+                              int32_t rows, int32_t cols, const double *intrinsics_dev /*[n][6]*/, uint8_t *out_dev);
+int  rcn_mvs_sweep_device(rcn_ctx *ctx, const uint8_t *gray_dev, int64_t stride_img_bytes, int64_t stride_row_bytes, int32_t n_images, int32_t rows, int32_t cols,
+                          const int32_t *views_host, int32_t V, int32_t S, const double *H_dev /*[V][S][D][9]*/, const double *inv_dev /*[V][D]*/, int32_t D,
+                          const rcn_mvs_options *opt, int16_t *plane_out_dev, float *depth_out_dev, float *cost_out_dev);
+int  rcn_mvs_consistency_device(rcn_ctx *ctx, const int32_t *views_host, int32_t V, int32_t S, const double *poses34_dev, const double *intrinsics_dev,
+                                int32_t n_images, int32_t rows, int32_t cols, const int16_t *plane_dev, const float *depth_dev, const rcn_mvs_options *opt,
+                                uint8_t *mask_out_dev, int32_t *counts_out_dev);
+int  rcn_mvs_fuse_device(rcn_ctx *ctx, const int32_t *views_host, int32_t V, int32_t S, const double *poses34_dev, const double *intrinsics_dev, int32_t n_images,
+                         const uint8_t *rgb_dev, int32_t rows, int32_t cols, const float *depth_dev, const uint8_t *mask_dev, const rcn_mvs_options *opt,
+                         int64_t capacity, void *vertices_out_dev, int64_t *counts_out_dev);
+/* Sources and depth ranges for every camera of a session in one call, computed on the device: sources_out [n_cams][S] = each
+ * camera's S most covisible cameras (rcn_ba_session_covisible's rule: shared landmarks descending, ties to the lower index,
+ * -1 where fewer share any); range_out [n_cams][2] = the smallest and largest positive camera-frame depth
+ * ((P[8] X + P[9] Y) + P[10] Z) + P[11] of the landmarks it observes, (0, 0) when there is none; covisible_out (may be NULL)
+ * [n_cams][n_cams]: the shared-landmark counts, the diagonal a camera's own landmarks.  poses34_host: the cameras as the
+ * pipeline holds them, as rcn_ba_session_validity takes them.  Waits.  The caller widens the range by a factor of its choice. */
+int  rcn_ba_session_mvs_views(rcn_ba_session *s, const double *poses34_host, int32_t S, int32_t *sources_out, double *range_out, int32_t *covisible_out);
 
 #ifdef __cplusplus
 }

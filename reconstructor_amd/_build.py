@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "librcn.so")
 SO_DIAG = os.path.join(ROOT, "tools", "librcn_diag.so")
-SOURCES = ["ctx.hip", "match.hip", "ba.hip", "ba_tied.hip", "chol.hip", "ba_session.hip", "ba_local.hip", "validity.hip", "triangulate.hip", "corr2d3d.hip", "pnp.hip", "twoview.hip", "homography.hip", "fmat.hip", "shard.hip", "store.hip", "desc.hip", "keypoints.hip", "superglue.hip", "superglue_gnn.hip", "superpoint_net.hip", "sift.hip", "orb.hip", "hamming.hip", "guided.hip", "tracks.hip", "retrieval.hip", "imgprep.hip"]
+SOURCES = ["ctx.hip", "match.hip", "ba.hip", "ba_tied.hip", "chol.hip", "ba_session.hip", "ba_local.hip", "validity.hip", "triangulate.hip", "corr2d3d.hip", "pnp.hip", "twoview.hip", "homography.hip", "fmat.hip", "shard.hip", "store.hip", "desc.hip", "keypoints.hip", "superglue.hip", "superglue_gnn.hip", "superpoint_net.hip", "sift.hip", "orb.hip", "hamming.hip", "guided.hip", "tracks.hip", "retrieval.hip", "imgprep.hip", "mvs.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 LIBS = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-z,defs"]      # -z defs: an unresolved symbol fails the build, not the first dlopen

@@ -59,6 +59,8 @@ SYMBOLS = [
     "rcn_retr_assign_device", "rcn_retr_encode_device", "rcn_retr_similarity_device", "rcn_retr_topk_device", "rcn_retr_pairs_device", "rcn_retr_image_pairs",
     "rcn_img_reshape_size", "rcn_img_resize_tables", "rcn_img_default_options", "rcn_img_prepare_plan", "rcn_img_prepare_device",
     "rcn_feat_colors_device", "rcn_landmark_colors_device", "rcn_cloud_vertices_device", "rcn_cloud_write_ply",
+    "rcn_mvs_default_options", "rcn_mvs_layout", "rcn_mvs_inv_depths", "rcn_mvs_homographies", "rcn_img_undistort_device",
+    "rcn_mvs_sweep_device", "rcn_mvs_consistency_device", "rcn_mvs_fuse_device", "rcn_ba_session_mvs_views",
     "rcn_store_save", "rcn_store_open", "rcn_store_contents_of", "rcn_store_close", "rcn_store_upload",
 ]
 SHARD_ID_BYTES = 128
@@ -173,6 +175,16 @@ class GuidedOptions(C.Structure):
 
 class TracksOptions(C.Structure):
     _fields_ = [("min_length", C.c_int32), ("max_length", C.c_int32), ("conflict", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MvsOptions(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("min_sources", C.c_int32), ("min_consistent", C.c_int32), ("stride", C.c_int32),
+                ("max_cost", C.c_double), ("rel_tol", C.c_double)]
+
+
+class MvsSizes(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("lds_bytes", C.c_int32),
+                ("pixels", C.c_int64), ("h_doubles", C.c_int64), ("samples", C.c_int64)]
 
 
 class RetrOptions(C.Structure):
@@ -614,6 +626,24 @@ def load():
     L.rcn_ba_session_init_pair.restype = C.c_int
     L.rcn_ba_session_init_pair.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(TwoViewOptions), C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp,
                                            C.POINTER(i32)]
+    L.rcn_mvs_default_options.restype = None
+    L.rcn_mvs_default_options.argtypes = [C.POINTER(MvsOptions)]
+    L.rcn_mvs_layout.restype = C.c_int
+    L.rcn_mvs_layout.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(MvsSizes)]
+    L.rcn_mvs_inv_depths.restype = C.c_int
+    L.rcn_mvs_inv_depths.argtypes = [C.c_double, C.c_double, i32, vp]
+    L.rcn_mvs_homographies.restype = C.c_int
+    L.rcn_mvs_homographies.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp]
+    L.rcn_img_undistort_device.restype = C.c_int
+    L.rcn_img_undistort_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32, vp, vp]
+    L.rcn_mvs_sweep_device.restype = C.c_int
+    L.rcn_mvs_sweep_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp, i32, C.POINTER(MvsOptions), vp, vp, vp]
+    L.rcn_mvs_consistency_device.restype = C.c_int
+    L.rcn_mvs_consistency_device.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, C.POINTER(MvsOptions), vp, vp]
+    L.rcn_mvs_fuse_device.restype = C.c_int
+    L.rcn_mvs_fuse_device.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, C.POINTER(MvsOptions), i64, vp, vp]
+    L.rcn_ba_session_mvs_views.restype = C.c_int
+    L.rcn_ba_session_mvs_views.argtypes = [vp, vp, i32, vp, vp, vp]
     L.rcn_store_save.restype = C.c_int
     L.rcn_store_save.argtypes = [C.c_char_p, C.POINTER(StoreContents)]
     L.rcn_store_open.restype = C.c_int

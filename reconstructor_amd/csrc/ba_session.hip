@@ -393,6 +393,24 @@ int rcn_ba_session_covisible(rcn_ba_session *s, int32_t cam, int32_t k, int32_t 
     return RCN_OK;
 }
 
+int rcn_ba_session_mvs_views(rcn_ba_session *s, const double *poses34_host, int32_t S, int32_t *sources_out, double *range_out, int32_t *covisible_out)
+{
+    if (!s) return RCN_ERR_ARG;
+    rcn_ctx *ctx = s->ctx;
+    const char *who = "rcn_ba_session_mvs_views";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int32_t nc = (int32_t)(s->poses.size() / 6), np = (int32_t)s->tracks.size();
+    if (S < 1 || S > RCN_MVS_MAX_SOURCES) { ctx->set_error(std::string(who) + ": S outside 1 .. 16"); return RCN_ERR_ARG; }
+    if (nc > 0 && (!poses34_host || !sources_out || !range_out)) { ctx->set_error(std::string(who) + ": null pointer"); return RCN_ERR_ARG; }
+    if (nc > 16384) { ctx->set_error(std::string(who) + ": more than 16384 cameras"); return RCN_ERR_ARG; }
+    if (nc == 0) return RCN_OK;
+    SES_HIP(hipSetDevice(ctx->device));
+    int rc = sync_observations(s);
+    if (rc) return rc;
+    return rcn_int_mvs_views(ctx, nc, np, s->ocam.as<int32_t>(), s->pt_off.as<int32_t>(), static_cast<const double *>(s->pts.p), poses34_host, S, sources_out, range_out,
+                             covisible_out);
+}
+
 int rcn_ba_session_set_loss(rcn_ba_session *s, const rcn_ba_loss *loss)
 {
     if (!s) return RCN_ERR_ARG;

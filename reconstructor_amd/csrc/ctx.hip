@@ -8,9 +8,9 @@ extern "C" {
 const char *rcn_version(void)
 {
 #ifdef RCN_DIAG
-    return "reconstructor_amd 0.18 (gfx950) DIAGNOSTIC BUILD";
+    return "reconstructor_amd 0.19 (gfx950) DIAGNOSTIC BUILD";
 #else
-    return "reconstructor_amd 0.18 (gfx950)";
+    return "reconstructor_amd 0.19 (gfx950)";
 #endif
 }
 
@@ -94,6 +94,7 @@ void rcn_destroy(rcn_ctx *ctx)
     rcn_int_ham_release(ctx);
     rcn_int_guided_release(ctx);
     rcn_int_tracks_release(ctx);
+    rcn_int_mvs_release(ctx);
     DevBuf *bufs[] = {&ctx->img_table, &ctx->pairs_dev, &ctx->groups_dev, &ctx->cand, &ctx->owner,
                       &ctx->fb_list, &ctx->sv_list, &ctx->counters, &ctx->out_tmp, &ctx->cnt_tmp, &ctx->scale_dev, &ctx->desc_bad, &ctx->kp_ws, &ctx->sg_ws, &ctx->sg_scores, &ctx->gnn_ws, &ctx->gnn_mdesc, &ctx->sp_ws, &ctx->sp_out, &ctx->sift_ws, &ctx->sift_pyr, &ctx->retr_ws, &ctx->retr_out, &ctx->img_ws, &ctx->orb_ws, &ctx->orb_pyr, &ctx->orb_tab};
     for (DevBuf *b : bufs) b->release();

@@ -309,6 +309,12 @@ struct rcn_ctx {
     bool trk_stage_pending = false;
     hipEvent_t trk_tev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool trk_timed = false;
+    // plane sweep (mvs.hip): the view table of one call and its staging (uploaded asynchronously; mvs_ev marks the copy), the row
+    // counts and offsets of the fusion
+    DevBuf mvs_tab, mvs_ws;
+    std::vector<int32_t> mvs_stage_host;
+    hipEvent_t mvs_ev = nullptr;
+    bool mvs_stage_pending = false;
     HamState *ham = nullptr;            // hamming.hip: created by the first rcn_bits_* / Hamming call, released by rcn_int_ham_release
     CholState chol;                     // the dense factorisation of the reduced system (chol.h, chol.hip)
     BaProbe *ba_probe = nullptr;        // tools/ba_step_check.hip only: one LM iteration copied out (above)
@@ -442,4 +448,7 @@ int rcn_int_resolve_scale(rcn_ctx *ctx);     // host copies of scale / bias / ma
 int rcn_int_match_grid(rcn_ctx *ctx, const int32_t *pairs_host, int32_t n_pairs, float ratio,
                        int32_t *out_dev, int64_t out_stride, int32_t *counts_dev);
 void rcn_int_tracks_release(rcn_ctx *ctx);   // tracks.hip: the track builder's buffers and events (rcn_destroy)
+int rcn_int_mvs_views(rcn_ctx *ctx, int32_t nc, int32_t np, const int32_t *ocam, const int32_t *pt_off, const double *pts, const double *poses34_host, int32_t S,
+                      int32_t *sources_out, double *range_out, int32_t *cov_out);      // mvs.hip: rcn_ba_session_mvs_views behind the session's lock
+void rcn_int_mvs_release(rcn_ctx *ctx);      // mvs.hip: the plane sweep's buffers and event (rcn_destroy)
 void rcn_int_guided_release(rcn_ctx *ctx);   // guided.hip: the guided matcher's buffers (rcn_destroy)
