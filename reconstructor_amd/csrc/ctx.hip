@@ -60,6 +60,8 @@ int rcn_create(int device_id, rcn_ctx **out)
     ctx->force_exact = fe && fe[0] == '1';
     const char *mi8 = std::getenv("RCN_MID_I8");
     ctx->mid_i8_off = mi8 && mi8[0] == '0';
+    const char *mi8m = std::getenv("RCN_MID_I8_MFMA");
+    ctx->mid_i8_dot4 = mi8m && mi8m[0] == '0';
     const char *rrp = std::getenv("RCN_RERANK_PASS");
     ctx->rerank_pass = rrp && rrp[0] == '1';
     const char *flp = std::getenv("RCN_FILTER_PASS");

@@ -15,7 +15,7 @@
 #define RCN_I8_IDX_BITS 12  // train-row bits of an int8 key
 #define RCN_MIDCAP 32       // candidates kept per row of the middle tier
 #define RCN_UNIQ_LDS 8192   // train rows whose owner table (K3, k_unique_pair) fits LDS
-#define MI8_TR 512          // k_mid_eval_i8 (mid_i8.h): train rows per tile, two per thread
+#define MI8_TR 512          // k_mid_eval_i8 (mid_i8.h): train rows per tile, 128 per wave
 #define MI8_TILES ((1 << RCN_I8_IDX_BITS) / MI8_TR)   // tiles of the largest image the int8 path admits
 
 namespace grid {

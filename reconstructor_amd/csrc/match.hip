@@ -1889,35 +1889,80 @@ __global__ void k_unique_emit(const ImgDev *__restrict__ imgs, const int32_t *__
 }
 
 // K3, one launch: a workgroup per pair with the owner table of the pair's train rows in LDS
-// (K2 <= 8192): claim with ds_min, emit, count -- the match table is read once and only the
-// entries that change are rewritten.
+// (K2 <= 8192): claim with ds_min, emit, count.  The table moves in 16-byte groups of four entries (when its rows are made of whole
+// groups; entry by entry otherwise); a row of up to UQ_REG_ROWS entries stays in registers between the claim and the emit, so the
+// table is read once, a longer one is read again.  Only the groups in which an entry changes are rewritten.
+#define UQ_REG_ROWS 4096       // 256 threads x 4 groups x 4 entries
+static_assert(RCN_UNIQ_LDS % 4 == 0 && UQ_REG_ROWS % 1024 == 0, "the owner table and a register row are whole groups");
+__device__ __forceinline__ void uq_claim4(const int4 v, int q0, int Kq, int *owner)
+{
+    if (q0 < Kq && v.x >= 0) atomicMin(&owner[v.x], q0);
+    if (q0 + 1 < Kq && v.y >= 0) atomicMin(&owner[v.y], q0 + 1);
+    if (q0 + 2 < Kq && v.z >= 0) atomicMin(&owner[v.z], q0 + 2);
+    if (q0 + 3 < Kq && v.w >= 0) atomicMin(&owner[v.w], q0 + 3);
+}
+// entries q0 .. q0 + 3 as they stand in the table (v) -> what stays of them; the tail beyond Kq is defined as -1.  Returns the entries kept.
+__device__ __forceinline__ int uq_emit4(int32_t *at, const int4 v, int q0, int Kq, const int *owner)
+{
+    // (an entry below Kq that holds no match stays what it is)
+    auto stay = [&](int tr, int q) { return q < Kq ? (tr < 0 || owner[tr] == q ? tr : -1) : -1; };
+    const int4 n = make_int4(stay(v.x, q0), stay(v.y, q0 + 1), stay(v.z, q0 + 2), stay(v.w, q0 + 3));
+    if (n.x != v.x || n.y != v.y || n.z != v.z || n.w != v.w) *reinterpret_cast<int4 *>(at) = n;
+    return (n.x >= 0) + (n.y >= 0) + (n.z >= 0) + (n.w >= 0);
+}
 __global__ __launch_bounds__(256) void k_unique_pair(const ImgDev *__restrict__ imgs, const int32_t *__restrict__ pairs,
                                                      int32_t *__restrict__ out, int64_t out_stride,
                                                      int32_t *__restrict__ counts, int pair_base)
 {
-    __shared__ int owner[RCN_UNIQ_LDS];
+    __shared__ __attribute__((aligned(16))) int owner[RCN_UNIQ_LDS];
     __shared__ int wsum[4];
     const int pair = pair_base + blockIdx.x, t = threadIdx.x;
     const int Kq = imgs[pairs[2 * pair]].K, Kt = imgs[pairs[2 * pair + 1]].K;
-    for (int i = t; i < Kt; i += 256) owner[i] = 0x7fffffff;
+    // whole groups of four: the last one may reach past Kt, never past the table (Kt <= RCN_UNIQ_LDS, which is a multiple of 4)
+    const int4 nobody = make_int4(0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff);
+    for (int i = t; 4 * i < Kt; i += 256) reinterpret_cast<int4 *>(owner)[i] = nobody;
     __syncthreads();
     int32_t *row = out + (size_t)pair * out_stride;
-    for (int q = t; q < Kq; q += 256) {
-        const int tr = row[q];
-        if (tr >= 0) atomicMin(&owner[tr], q);
-    }
-    __syncthreads();
     int kept = 0;
-    for (int q0 = 0; q0 < out_stride; q0 += 256) {
-        const int q = q0 + t;
-        bool keep = false;
-        if (q < out_stride) {
-            const int tr = q < Kq ? row[q] : -1;
-            keep = tr >= 0 && owner[tr] == q;
-            if (!keep && (q >= Kq || tr >= 0)) row[q] = -1;      // the tail beyond Kq is defined as -1
+    if ((out_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        // rows of whole 16-byte groups: four entries per lane and round, 4 KiB per workgroup instruction
+        if (out_stride <= UQ_REG_ROWS) {
+            // the row stays in registers between the two phases: the table is read once
+            int4 v[UQ_REG_ROWS / 1024];
+#pragma unroll
+            for (int k = 0; k < UQ_REG_ROWS / 1024; ++k) {
+                const int q0 = 4 * (k * 256 + t);
+                v[k] = make_int4(-1, -1, -1, -1);
+                if (q0 < out_stride) v[k] = *reinterpret_cast<const int4 *>(row + q0);
+            }
+#pragma unroll
+            for (int k = 0; k < UQ_REG_ROWS / 1024; ++k) uq_claim4(v[k], 4 * (k * 256 + t), Kq, owner);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < UQ_REG_ROWS / 1024; ++k) {
+                const int q0 = 4 * (k * 256 + t);
+                if (q0 < out_stride) kept += uq_emit4(row + q0, v[k], q0, Kq, owner);
+            }
+        } else {
+            for (int q0 = 4 * t; q0 < Kq; q0 += 1024) uq_claim4(*reinterpret_cast<const int4 *>(row + q0), q0, Kq, owner);
+            __syncthreads();
+            for (int q0 = 4 * t; q0 < out_stride; q0 += 1024) kept += uq_emit4(row + q0, *reinterpret_cast<const int4 *>(row + q0), q0, Kq, owner);
         }
-        kept += (int)__popcll(__ballot(keep));
+    } else {
+        for (int q = t; q < Kq; q += 256) {
+            const int tr = row[q];
+            if (tr >= 0) atomicMin(&owner[tr], q);
+        }
+        __syncthreads();
+        for (int q = t; q < out_stride; q += 256) {
+            const int tr = q < Kq ? row[q] : -1;
+            const bool keep = tr >= 0 && owner[tr] == q;
+            if (!keep && (q >= Kq || tr >= 0)) row[q] = -1;      // the tail beyond Kq is defined as -1
+            kept += keep;
+        }
     }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) kept += __shfl_xor(kept, o);
     if ((t & 63) == 0) wsum[t >> 6] = kept;
     __syncthreads();
     if (t == 0) counts[pair] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -2635,7 +2680,15 @@ static int launch_mid_tier(rcn_ctx *ctx, const grid::GridPlan &pl, const RerankA
     k_mid_bins<<<1, 1024, 0, st>>>(ma);
     k_mid_scatter<<<cus * 4, 256, 0, st>>>(ma);
     k_mid_eval<<<cus * 4, 256, 0, st>>>(ma);
-    if (pl.mid_i8) k_mid_eval_i8<<<dim3((unsigned)n_slots * MI8_TILES, (unsigned)pl.mid_i8_grid_y), 256, 0, st>>>(ma);
+    if (pl.mid_i8) {
+        const dim3 g8((unsigned)n_slots * MI8_TILES, (unsigned)pl.mid_i8_grid_y);
+#ifdef RCN_DIAG
+        ctx->mid_i8_launched = ctx->mid_i8_dot4 ? 2 : 1;
+        if (ctx->mid_i8_dot4) k_mid_eval_i8_dot4<<<g8, 256, 0, st>>>(ma);
+        else
+#endif
+        k_mid_eval_i8<<<g8, 256, 0, st>>>(ma);
+    }
     launch_mid_exact(ctx, ma, st);
     RCN_HIP(hipGetLastError());
     // K2b: the overflow list (the tier runs only where rows are read as float4)
@@ -3146,6 +3199,50 @@ int rcn_diag_mid(rcn_ctx *ctx, int64_t *n_rows, unsigned long long *sorted_host,
     if (ccount_host) RCN_HIP(hipMemcpyAsync(ccount_host, mw + mo.cc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (clist_host) RCN_HIP(hipMemcpyAsync(clist_host, mw + mo.cl, n * 4 * RCN_MIDCAP, hipMemcpyDeviceToHost, ctx->stream));
     RCN_HIP(hipStreamSynchronize(ctx->stream));
+    return RCN_OK;
+}
+
+// Diagnostic build only: the form of the int8 sweep the last pass of the middle tier launched -- 0 none, 1 k_mid_eval_i8 (MFMA),
+// 2 k_mid_eval_i8_dot4 (RCN_MID_I8_MFMA=0) -- so that a differential test knows that its two arms ran two kernels.
+int rcn_diag_mid_sweep(rcn_ctx *ctx)
+{
+    if (!ctx) return RCN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return ctx->mid_i8_launched;
+}
+
+// Diagnostic build only: k_unique_pair alone on a table of the caller's.  Pair p has kq_kt_host[2 p] query rows and kq_kt_host[2 p + 1]
+// train rows (at most RCN_UNIQ_LDS; every non-negative entry below kq must be a train row below kt, kq <= stride); table_dev is
+// rewritten in place, counts_dev[p] receives the entries kept.  Waits.
+int rcn_diag_unique_pair(rcn_ctx *ctx, const int32_t *kq_kt_host, int32_t n_pairs, int32_t *table_dev, int64_t stride, int32_t *counts_dev)
+{
+    if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!kq_kt_host || !table_dev || !counts_dev))) return RCN_ERR_ARG;
+    if (n_pairs == 0) return RCN_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    std::vector<ImgDev> imgs(2 * (size_t)n_pairs);
+    std::vector<int32_t> pr(2 * (size_t)n_pairs);
+    for (int i = 0; i < 2 * n_pairs; ++i) {
+        const int32_t k = kq_kt_host[i];
+        if (k < 0 || ((i & 1) ? k > RCN_UNIQ_LDS : k > stride)) { ctx->set_error("rcn_diag_unique_pair: a row count the kernel does not take"); return RCN_ERR_ARG; }
+        memset(&imgs[i], 0, sizeof(ImgDev));
+        imgs[i].K = k;
+        pr[i] = i;
+    }
+    RCN_HIP(hipSetDevice(ctx->device));
+    ImgDev *di = nullptr;
+    int32_t *dp = nullptr;
+    if (hipMalloc(&di, imgs.size() * sizeof(ImgDev)) != hipSuccess || hipMalloc(&dp, pr.size() * sizeof(int32_t)) != hipSuccess) { (void)hipFree(di); return RCN_ERR_HIP; }
+    hipError_t e = hipMemcpyAsync(di, imgs.data(), imgs.size() * sizeof(ImgDev), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp, pr.data(), pr.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        k_unique_pair<<<n_pairs, 256, 0, ctx->stream>>>(di, dp, table_dev, stride, counts_dev, 0);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(di);
+    (void)hipFree(dp);
+    RCN_HIP(e);
+    RCN_HIP(es);
     return RCN_OK;
 }
 #endif

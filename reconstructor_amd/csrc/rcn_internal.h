@@ -244,6 +244,8 @@ struct rcn_ctx {
     int ablate = 0;            // RCN_COARSE_ABL
     bool force_exact = false;  // RCN_FORCE_EXACT=1: skip the MFMA coarse pass
     bool mid_i8_off = false;   // RCN_MID_I8=0: on the int8 path too, every row of the middle tier takes the fp32 sweep (no k_mid_eval_i8)
+    bool mid_i8_dot4 = false;  // RCN_MID_I8_MFMA=0: the int8 sweep of the middle tier on v_dot4 (k_mid_eval_i8_dot4), the differential reference of the MFMA form
+    int mid_i8_launched = 0;   // which form of the int8 sweep the last pass of the middle tier launched (rcn_diag_mid_sweep): 0 none, 1 MFMA, 2 dot4
     bool rerank_pass = false;  // RCN_RERANK_PASS=1: certify's verdict is ignored, every re-ranked row goes to the middle tier
     bool filter_pass = false;  // RCN_FILTER_PASS=1: k_filter certifies nothing, every row with a coarse pair goes to the re-rank
     bool no_item_order = false;   // RCN_MATCH_NO_ORDER=1: work items in pair order instead of heaviest-first per XCD

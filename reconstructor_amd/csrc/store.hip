@@ -24,7 +24,13 @@ __global__ __launch_bounds__(1024) void k_cmp_scan(const int32_t *__restrict__ c
     if (threadIdx.x == 1023) off[n] = total;
 }
 
-// one workgroup per pair: ordered compaction of the row (ascending query index) by ballots
+// one workgroup per pair: ordered compaction of the row (ascending query index).  Never past the pair's range: a table whose
+// non-negative entries outnumber counts[pair] (not yet through the uniqueness pass, stale counts) loses its surplus instead of
+// overwriting the next pair's list.
+// A table of whole 16-byte groups (VEC) moves four entries per lane and round -- thread t owns entries 4 t .. 4 t + 3 of the round's
+// 1024, ranked by a workgroup scan of the per-thread counts, the next round's group requested before the scan -- any other table one
+// entry per lane and round, ranked by ballots.
+template <bool VEC>
 __global__ __launch_bounds__(256) void k_cmp_fill(const int32_t *__restrict__ table, int64_t stride,
                                                   const int32_t *__restrict__ counts, const long long *__restrict__ off,
                                                   int2 *__restrict__ qt)
@@ -36,16 +42,38 @@ __global__ __launch_bounds__(256) void k_cmp_fill(const int32_t *__restrict__ ta
     const int32_t *row = table + (size_t)pair * stride;
     int2 *dst = qt + off[pair];
     int pos = 0;
-    for (int64_t q0 = 0; q0 < stride && pos < total; q0 += 256) {
-        const int64_t q = q0 + t;
-        const int tr = q < stride ? row[q] : -1;
-        int chunk;
-        const int at = pos + wg_rank<256>(tr >= 0, wsum, chunk);
-        // never past the pair's range: a table whose non-negative entries outnumber counts[pair] (not yet through the
-        // uniqueness pass, stale counts) loses its surplus instead of overwriting the next pair's list
-        if (tr >= 0 && at < total) dst[at] = make_int2((int)q, tr);
-        pos += chunk;
+    if (VEC) {
+        const int4 none = make_int4(-1, -1, -1, -1);
+        int4 v = 4 * t < stride ? *reinterpret_cast<const int4 *>(row + 4 * t) : none;
+        for (int64_t q0 = 0; q0 < stride && pos < total; q0 += 1024) {
+            const int64_t q = q0 + 4 * t, qn = q + 1024;
+            const int4 nx = qn < stride ? *reinterpret_cast<const int4 *>(row + qn) : none;
+            const int mine = (v.x >= 0) + (v.y >= 0) + (v.z >= 0) + (v.w >= 0);
+            int chunk;
+            int at = pos + wg_scan_incl<int, 256>(mine, wsum, chunk) - mine;
+            if (v.x >= 0) { if (at < total) dst[at] = make_int2((int)q, v.x); ++at; }
+            if (v.y >= 0) { if (at < total) dst[at] = make_int2((int)q + 1, v.y); ++at; }
+            if (v.z >= 0) { if (at < total) dst[at] = make_int2((int)q + 2, v.z); ++at; }
+            if (v.w >= 0 && at < total) dst[at] = make_int2((int)q + 3, v.w);
+            pos += chunk;
+            v = nx;
+        }
+    } else {
+        for (int64_t q0 = 0; q0 < stride && pos < total; q0 += 256) {
+            const int64_t q = q0 + t;
+            const int tr = q < stride ? row[q] : -1;
+            int chunk;
+            const int at = pos + wg_rank<256>(tr >= 0, wsum, chunk);
+            if (tr >= 0 && at < total) dst[at] = make_int2((int)q, tr);
+            pos += chunk;
+        }
     }
+}
+
+void launch_cmp_fill(hipStream_t st, const int32_t *table, int64_t stride, const int32_t *counts, const long long *off, int32_t n_pairs, int2 *qt)
+{
+    if ((stride & 3) == 0 && (reinterpret_cast<uintptr_t>(table) & 15) == 0) k_cmp_fill<true><<<n_pairs, 256, 0, st>>>(table, stride, counts, off, qt);
+    else k_cmp_fill<false><<<n_pairs, 256, 0, st>>>(table, stride, counts, off, qt);
 }
 
 }  // namespace
@@ -85,7 +113,7 @@ int rcn_match_compact_wait(rcn_ctx *ctx)
 // shard.hip (rcn_shard_gather_lists): the ordered compaction alone, no copy to the host
 void rcn_int_launch_cmp_fill(hipStream_t st, const int32_t *table_dev, int64_t stride, const int32_t *counts_dev, const long long *off, int32_t n_pairs, int2 *qt)
 {
-    k_cmp_fill<<<n_pairs, 256, 0, st>>>(table_dev, stride, counts_dev, off, qt);
+    launch_cmp_fill(st, table_dev, stride, counts_dev, off, n_pairs, qt);
 }
 
 // the two above with ctx->mu held by the caller (rcn_shard_lists keeps it across table lookup, compaction and wait)
@@ -130,7 +158,7 @@ int rcn_int_compact_begin(rcn_ctx *ctx, const int32_t *table_dev, int64_t stride
         if (ctx->cmp_busy[b]) RCN_HIP(hipEventSynchronize(ctx->cmp_ev[b]));
         RCN_HIP(ctx->cmp_qt[b].reserve((size_t)total * sizeof(int2)));
     }
-    k_cmp_fill<<<n_pairs, 256, 0, st>>>(table_dev, stride, counts_dev, off, ctx->cmp_qt[b].as<int2>());
+    launch_cmp_fill(st, table_dev, stride, counts_dev, off, n_pairs, ctx->cmp_qt[b].as<int2>());
     RCN_HIP(hipGetLastError());
     RCN_HIP(hipEventRecord(ctx->cmp_filled, st));
     RCN_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->cmp_filled, 0));
